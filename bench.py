@@ -19,6 +19,26 @@ steps (every step re-tokenizes and rebuilds the index from scratch).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload config3|config5|config5share]
                     [--scaling strong|weak] [--rank-share r/N] [--letter-split reference|balanced]
+                    [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and no more: it generates the
+corpus, uploads it, warms up, times the K steps, writes its outputs when
+--dump-outputs is given, and prints the JSON line (value, ms_per_step, the
+rooflines and counts of the timed steps).  --full adds everything else, each
+in a run of its own after the timed loop: the verification against the
+oracle's hashes, the CPU baselines and the configs[1] lane, the file-reader
+and end-to-end legs, and the export leg of --rank-share (each can still be
+switched off: --no-verify, --no-cpu-baseline, --io-bytes 0).
+
+--dump-outputs DIR: after the timed steps, what the last timed step left for
+its caller (ii_device_text: the formatted index in device memory and its 27
+letter offsets; ii_get_stats' counts) is written as DIR/<name>.npy —
+letter_offsets (float64[27]), letter_byte_sums (float64[26], the sum of each
+letter's bytes, exact), counts (float64: tokens, words, pairs, out_bytes) and
+text_sample (float32: the whole text up to 8 MiB, else 256 blocks of 32 KiB at
+fixed seeded positions, the first and the last block among them).  The corpus
+is a function of the arguments alone, so two builds can be compared array by
+array.  With N > 1 every rank writes its own <name>_rank<r>.npy.
 
 --rank-share r/N (one GPU): the share of rank r when the workload is strong-
 scaled over N GPUs — the files ii_partition (M = N, main.c:300-323) gives
@@ -40,10 +60,10 @@ R = N, main.c:129-130, as north_star asks; --letter-split balanced: the
 histogram-balanced ranges of SURVEY §8 f4), and the owners merge and format.
 --scaling weak: every rank indexes its own full-size corpus (seed + 1000*rank).
 
-After the timed loop (outside it) one more step copies the text out and every
-letter's sha256 is compared with tests/golden/bench_hashes.json (made by the
-oracle in the build container): "verified" in the JSON line.  Rank 0 prints
-ONE JSON line.
+With --full, after the timed loop (outside it) one more step copies the text
+out and every letter's sha256 is compared with tests/golden/bench_hashes.json
+(made by the oracle in the build container): "verified" in the JSON line
+(null in a plain run).  Rank 0 prints ONE JSON line.
 """
 import argparse
 import hashlib
@@ -110,7 +130,14 @@ def parse():
     p.add_argument("--rank-share", default=None, metavar="r/N",
                    help="one GPU: index rank r's ii_partition share of the workload strong-scaled over N GPUs, "
                         "with its global file ids")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, < 64 MB)")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also verify against the oracle's hashes and run the CPU baselines, "
+                        "the configs[1] lane, the file-reader / end-to-end legs and --rank-share's export leg")
     a = p.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        p.error("--steps needs K >= 1 and --warmup W >= 0")
     a.share = None
     if a.rank_share:
         r, _, n = a.rank_share.partition("/")
@@ -119,6 +146,8 @@ def parse():
             p.error("--rank-share r/N needs 0 <= r < N")
     if a.no_cpu_baseline:
         a.cpu_baseline = "none"
+    if not a.full:  # a plain run: the timed steps (and --dump-outputs) alone
+        a.cpu_baseline, a.io_bytes, a.no_verify = "none", 0, True
     w = WORKLOADS[a.workload]
     a.custom = any(v is not None for v in (a.bytes, a.files, a.vocab, a.seed))
     a.bytes = int(a.bytes if a.bytes is not None else w["bytes"])
@@ -467,6 +496,53 @@ def io_legs(idx, text, off, io_bytes, cores):
         shutil.rmtree(td, ignore_errors=True)
 
 
+DUMP_WHOLE = 8 << 20  # a text up to this size is dumped whole
+DUMP_BLOCK, DUMP_BLOCKS = 32 << 10, 256  # else: 256 blocks of 32 KiB (8 MiB of text, 32 MiB as float32)
+
+
+def sample_starts(total):
+    """Start offsets of the text blocks --dump-outputs samples from a text of
+    `total` bytes: the first and the last block and seeded positions between
+    (a function of `total` alone, ascending)."""
+    import numpy as np
+    if total <= DUMP_WHOLE:
+        return [0]
+    last = total - DUMP_BLOCK
+    mid = np.random.default_rng(20240229).integers(0, last + 1, DUMP_BLOCKS - 2)
+    return sorted([0, last] + [int(x) for x in mid])
+
+
+def dump_outputs(idx, st, outdir, suffix=""):
+    """What the last step left for its caller, as outdir/<name><suffix>.npy:
+    the device-resident index text (ii_device_text; read where it lies, not
+    recomputed) as per-letter offsets, per-letter byte sums and a fixed sample,
+    and ii_get_stats' counts."""
+    import numpy as np
+    import torch
+
+    class DeviceBytes:  # the library's own buffer as a torch tensor (no copy; only read here)
+        def __init__(self, ptr, n):
+            self.__cuda_array_interface__ = {"shape": (n,), "typestr": "|u1", "data": (ptr, False), "version": 2}
+
+    ptr, off = idx.device_text()
+    total = int(off[-1])
+    os.makedirs(outdir, exist_ok=True)
+    sums = np.zeros(26, dtype=np.float64)
+    if total:
+        text = torch.as_tensor(DeviceBytes(ptr, total), device="cuda")
+        for l in range(26):
+            if off[l + 1] > off[l]:
+                sums[l] = float(text[off[l]:off[l + 1]].sum(dtype=torch.int64).item())  # < 2^53: exact
+        size = total if total <= DUMP_WHOLE else DUMP_BLOCK
+        sample = torch.cat([text[s:s + size] for s in sample_starts(total)]).to(torch.float32).cpu().numpy()
+    else:
+        sample = np.zeros(0, dtype=np.float32)
+    arrays = {"letter_offsets": np.asarray(off, dtype=np.float64), "letter_byte_sums": sums, "text_sample": sample,
+              "counts": np.asarray([st.tokens, st.words, st.pairs, st.out_bytes], dtype=np.float64)}
+    for name, arr in arrays.items():
+        np.save(os.path.join(outdir, "%s%s.npy" % (name, suffix)), arr)
+
+
 def main():
     a = parse()
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -589,9 +665,14 @@ def main():
     ms_per_step = dt / a.steps * 1e3
     value = total_bytes * a.steps / dt / 1e9
 
-    # ---- --rank-share: what the rank does before the exchange (map + local reduce + export), timed apart
+    # ---- --dump-outputs: what the last timed step left in the context (N > 1: this rank's letters)
+    if a.dump_outputs:
+        log("writing the outputs of the last timed step to %s" % a.dump_outputs)
+        dump_outputs(idx, idx.stats(), a.dump_outputs, "_rank%d" % rank if world > 1 else "")
+
+    # ---- --full --rank-share: what the rank does before the exchange (map + local reduce + export), timed apart
     export_leg = None
-    if a.share:
+    if a.share and a.full:
         parts = a.share[1]
         send = None
         ts = []
@@ -697,8 +778,10 @@ def main():
             cpu = cpu_baseline(a, text, off)
             log("configs[1] lane: the reference and the GPU on test.txt")
             cpu["config2"] = config2_lane(idx)
-        log("file reader and end-to-end legs")
-        io, e2e = io_legs(idx, text, off, a.io_bytes, host_cores()) if world == 1 and a.io_bytes > 0 else (None, None)
+        io, e2e = None, None
+        if world == 1 and a.io_bytes > 0:
+            log("file reader and end-to-end legs")
+            io, e2e = io_legs(idx, text, off, a.io_bytes, host_cores())
         wl = WORKLOADS[a.workload]
         workload = "%s: %s" % (a.workload, wl["label"] if not a.custom else "zipf %.4g GB x %d files, vocab %d, seed %d"
                                % (a.bytes / 1e9, a.files, a.vocab, a.seed))
@@ -717,6 +800,7 @@ def main():
             "steps": a.steps,
             "warmup": a.warmup,
             "ms_per_step": round(ms_per_step, 3),
+            "full": a.full,
             "higher_is_better": True,
             # strong: one corpus whatever N (total work fixed); weak: a corpus per rank
             "scaling": "strong" if strong else "weak",

@@ -14,11 +14,11 @@ mkdir -p "$OUT"
 cd "$ROOT" || exit 1
 export TMPDIR=/tmp
 echo "== config5 share 0/8" && \
-timeout -k 10 400 python bench.py --workload config5 --rank-share 0/8 --steps 5 --warmup 2 --no-cpu-baseline \
+timeout -k 10 400 python bench.py --full --workload config5 --rank-share 0/8 --steps 5 --warmup 2 --no-cpu-baseline \
     --io-bytes 0 > "$OUT/share0.log" 2>&1 && tail -1 "$OUT/share0.log" | cut -c1-200 && \
 echo "== config5 share 7/8" && \
-timeout -k 10 400 python bench.py --workload config5 --rank-share 7/8 --steps 5 --warmup 2 --no-cpu-baseline \
+timeout -k 10 400 python bench.py --full --workload config5 --rank-share 7/8 --steps 5 --warmup 2 --no-cpu-baseline \
     --io-bytes 0 > "$OUT/share7.log" 2>&1 && tail -1 "$OUT/share7.log" | cut -c1-200 && \
 echo "== gloo x4 config3" && \
-II_DIST_BACKEND=gloo timeout -k 10 500 python bench.py --gpus 4 --steps 3 --warmup 1 > "$OUT/gloo4.log" 2>&1 && \
+II_DIST_BACKEND=gloo timeout -k 10 500 python bench.py --full --gpus 4 --steps 3 --warmup 1 > "$OUT/gloo4.log" 2>&1 && \
 tail -1 "$OUT/gloo4.log" | cut -c1-200

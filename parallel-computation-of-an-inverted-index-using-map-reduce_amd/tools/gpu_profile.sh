@@ -12,7 +12,7 @@ mkdir -p "$OUT"
 cd "$ROOT" || exit 1
 export TMPDIR=/tmp
 echo "== bench" && \
-timeout -k 10 500 python bench.py > "$OUT/bench.log" 2>&1 && tail -1 "$OUT/bench.log" | cut -c1-300 && \
+timeout -k 10 500 python bench.py --full > "$OUT/bench.log" 2>&1 && tail -1 "$OUT/bench.log" | cut -c1-300 && \
 echo "== rocprof" && \
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o run -- \
     python3 bench.py --steps 10 --warmup 1 --no-cpu-baseline --io-bytes 0 --no-verify > "$OUT/prof.log" 2>&1 && \

@@ -29,7 +29,7 @@ OUT="$ROOT/gpurun_out/$TAG"
 mkdir -p "$OUT"
 cd "$ROOT" || exit 1
 export TMPDIR=/tmp
-QB="--steps 10 --warmup 2 --no-cpu-baseline --io-bytes 0"
+QB="--full --steps 10 --warmup 2 --no-cpu-baseline --io-bytes 0"
 
 summ() {  # one bench line -> a short summary
     tail -1 "$1" | python3 -c "
@@ -54,7 +54,7 @@ step() {
         tail -3 "$OUT/pytest_gpu.log"
         return $rc ;;
     bench)
-        timeout -k 10 600 python bench.py > "$OUT/bench.log" 2>&1 && summ "$OUT/bench.log" bench ;;
+        timeout -k 10 600 python bench.py --full > "$OUT/bench.log" 2>&1 && summ "$OUT/bench.log" bench ;;
     quick)
         # shellcheck disable=SC2086
         timeout -k 10 300 python bench.py $QB $arg > "$OUT/quick.log" 2>&1 && summ "$OUT/quick.log" quick ;;

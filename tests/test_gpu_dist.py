@@ -144,7 +144,8 @@ def test_bench_two_ranks_gloo_strong_scaling():
     from oracle_py import oracle_index
     nb, nf, vocab, seed = 60_000_000, 400, 200_000, 3
     env = dict(os.environ, II_DIST_BACKEND="gloo")
-    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
+    # (--full: the per-letter hashes come from the verification step after the timed loop)
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--full", "--gpus", "2", "--steps", "2", "--warmup", "1",
                         "--bytes", str(nb), "--files", str(nf), "--vocab", str(vocab), "--seed", str(seed),
                         "--no-cpu-baseline", "--io-bytes", "0"], cwd=REPO, env=env, capture_output=True, timeout=300)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
