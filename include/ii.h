@@ -247,6 +247,61 @@ int ii_reducer_letters(int r, int R, int *lo, int *hi);
 int ii_partition(const uint64_t *sizes, uint32_t nfiles, int M, uint32_t *order, uint32_t *shard_begin,
                  uint32_t *shard_end);
 
+/*
+ * Boolean term queries on the device-resident partial index (no reference
+ * equivalent: the reference only prints the index).  Legal whenever the
+ * context holds a partial index: after ii_reduce, ii_reduce_local or
+ * ii_import (with or without ii_reduce following); II_ERR_STATE before any of
+ * them and after a later ii_map_*.  An owner of an exchange answers for the
+ * letters it owns only (every other word is absent there).  A query reads the
+ * index and writes buffers of its own: ii_letter_text, ii_device_text, the
+ * export calls and ii_reduce behave after it as before it.  After
+ * ii_map_device the caller's d_text must still be valid (terms longer than
+ * 12 letters are compared against the indexed text).
+ */
+#define II_MAX_QUERY_TERMS 16
+enum { II_Q_AND = 0, II_Q_OR = 1 };
+
+/* main.c:105-111 for one term: keep letters, lower-case them, at most
+ * II_MAX_WORD-1 of them; reading stops at n, at the first NUL or at the first
+ * C-locale whitespace byte (what fscanf("%s") would have handed the loop).
+ * Writes the cleaned word + NUL, returns its length (0 = matches nothing).
+ * Pure host arithmetic. */
+size_t ii_clean_term(const char *in, size_t n, char out[II_MAX_WORD]);
+
+/* df of every term (0 = absent).  Term t is terms[term_off[t] .. term_off[t+1]),
+ * raw bytes, cleaned by ii_clean_term's rule. */
+int ii_lookup(ii_ctx *ctx, const char *terms, const uint32_t *term_off,
+              uint32_t nterms, uint32_t *df_out);
+
+/* Query q combines terms [query_first[q], query_first[q+1]) with op
+ * (at most II_MAX_QUERY_TERMS of them, else II_ERR_ARG; term_off has
+ * query_first[nqueries] + 1 entries).
+ * II_Q_AND: the ids in every term's posting list (any term absent or cleaning
+ * to nothing: empty); II_Q_OR: the union (absent terms add nothing).  A query
+ * with no terms is empty.
+ * Result q = ids[res_off[q] .. res_off[q+1]): file ids AS PRINTED (id0 + 1),
+ * ascending, no repeats.  Host arrays owned by the context, valid until the
+ * next ii_query / ii_map_* / ii_import / ii_close on it.  res_off / res_ids
+ * may be NULL (both): the result then stays on the device (ii_query_device).
+ * Limit: a file with id0 = UINT32_MAX has no printed id that fits a u32; its
+ * postings are left out of every result. */
+int ii_query(ii_ctx *ctx, const char *terms, const uint32_t *term_off,
+             const uint32_t *query_first, uint32_t nqueries, int op,
+             const uint64_t **res_off, const uint32_t **res_ids);
+
+/* The same result, device-resident (no host copy is made if only this is
+ * wanted: pass NULL for res_off / res_ids above).  d_res_off has nqueries + 1
+ * entries.  Valid as long as the host arrays would be. */
+int ii_query_device(ii_ctx *ctx, const uint64_t **d_res_off, const uint32_t **d_res_ids);
+
+/* Counters of the last ii_query: postings_read = candidate postings the
+ * combine kernels loaded (AND: the driver lists, OR: every distinct list),
+ * ms_lookup / ms_combine device time, ms_total host wall time of the call. */
+typedef struct { uint32_t queries, terms, terms_found; uint64_t postings_read, ids_out;
+                 double ms_lookup, ms_combine, ms_total; } ii_query_stats;
+int ii_get_query_stats(ii_ctx *ctx, ii_query_stats *out);
+
 #ifdef __cplusplus
 }
 #endif

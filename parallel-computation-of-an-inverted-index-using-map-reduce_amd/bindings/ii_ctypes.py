@@ -53,6 +53,20 @@ class Stats(ctypes.Structure):
         return d
 
 
+class QueryStats(ctypes.Structure):
+    _fields_ = [("queries", ctypes.c_uint32), ("terms", ctypes.c_uint32), ("terms_found", ctypes.c_uint32),
+                ("postings_read", ctypes.c_uint64), ("ids_out", ctypes.c_uint64),
+                ("ms_lookup", ctypes.c_double), ("ms_combine", ctypes.c_double), ("ms_total", ctypes.c_double)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+MAX_WORD = 300
+MAX_QUERY_TERMS = 16
+Q_AND, Q_OR = 0, 1
+
+
 class IIFile(ctypes.Structure):
     _fields_ = [("path", ctypes.c_char_p), ("size", ctypes.c_uint64), ("id0", ctypes.c_uint32),
                 ("mapper", ctypes.c_int32)]
@@ -112,6 +126,15 @@ def lib():
         L.ii_partials.argtypes = [ctypes.c_void_p, u32p, ctypes.c_uint32]
         L.ii_partial_text.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_char_p),
                                       ctypes.POINTER(ctypes.c_size_t)]
+        if not var or hasattr(L, "ii_query"):  # (an A/B variant built from an older revision has no queries)
+            L.ii_clean_term.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p]
+            L.ii_clean_term.restype = ctypes.c_size_t
+            L.ii_lookup.argtypes = [ctypes.c_void_p, ctypes.c_char_p, u32p, ctypes.c_uint32, u32p]
+            L.ii_query.argtypes = [ctypes.c_void_p, ctypes.c_char_p, u32p, u32p, ctypes.c_uint32, ctypes.c_int,
+                                   ctypes.POINTER(u64p), ctypes.POINTER(u32p)]
+            L.ii_query_device.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p),
+                                          ctypes.POINTER(ctypes.c_void_p)]
+            L.ii_get_query_stats.argtypes = [ctypes.c_void_p, ctypes.POINTER(QueryStats)]
         _lib = L
     return _lib
 
@@ -253,11 +276,72 @@ class Index:
         _check(lib().ii_get_stats(self.h, ctypes.byref(s)), "ii_get_stats")
         return s
 
+    def lookup(self, terms):
+        """df of every term (bytes or str; 0 = absent), ii_lookup."""
+        blob, off = _pack_terms(terms)
+        df = np.zeros(max(1, len(terms)), dtype=np.uint32)
+        _check(lib().ii_lookup(self.h, blob, _u32(off), len(terms), _u32(df)), "ii_lookup")
+        return [int(x) for x in df[:len(terms)]]
+
+    def query(self, queries, op="and", to_host=True):
+        """queries: a list of lists of terms (bytes or str), each combined
+        with op ("and" / "or") -> one ascending uint32 array of printed file
+        ids per query.  to_host=False leaves the result on the device
+        (query_device) and returns None."""
+        opc = {"and": Q_AND, "or": Q_OR}.get(op, op)
+        blob, off = _pack_terms([t for q in queries for t in q])
+        first = np.zeros(len(queries) + 1, dtype=np.uint32)
+        if queries:
+            first[1:] = np.cumsum([len(q) for q in queries], dtype=np.uint64)
+        if not to_host:
+            _check(lib().ii_query(self.h, blob, _u32(off), _u32(first), len(queries), opc, None, None), "ii_query")
+            return None
+        roff = ctypes.POINTER(ctypes.c_uint64)()
+        rids = ctypes.POINTER(ctypes.c_uint32)()
+        _check(lib().ii_query(self.h, blob, _u32(off), _u32(first), len(queries), opc, ctypes.byref(roff),
+                              ctypes.byref(rids)), "ii_query")
+        o = np.ctypeslib.as_array(roff, shape=(len(queries) + 1,)).copy()
+        n = int(o[-1])
+        ids = np.ctypeslib.as_array(rids, shape=(n,)).copy() if n else np.zeros(0, dtype=np.uint32)
+        return [ids[int(o[q]):int(o[q + 1])] for q in range(len(queries))]
+
+    def query_device(self):
+        """(device pointer of the u64 result offsets, of the u32 ids) of the last query."""
+        po, pi = ctypes.c_void_p(), ctypes.c_void_p()
+        _check(lib().ii_query_device(self.h, ctypes.byref(po), ctypes.byref(pi)), "ii_query_device")
+        return po.value, pi.value
+
+    def query_stats(self):
+        s = QueryStats()
+        _check(lib().ii_get_query_stats(self.h, ctypes.byref(s)), "ii_get_query_stats")
+        return s
+
     def device_text(self):
         p = ctypes.c_void_p()
         off = (ctypes.c_uint64 * (ALPHABET + 1))()
         _check(lib().ii_device_text(self.h, ctypes.byref(p), off), "ii_device_text")
         return p.value, list(off)
+
+
+def _term_bytes(t):
+    return t.encode("utf-8", "surrogateescape") if isinstance(t, str) else bytes(t)
+
+
+def _pack_terms(terms):
+    """-> (blob, u32 offsets[len + 1]) of raw terms (bytes or str)."""
+    raw = [_term_bytes(t) for t in terms]
+    off = np.zeros(len(raw) + 1, dtype=np.uint32)
+    if raw:
+        off[1:] = np.cumsum([len(r) for r in raw], dtype=np.uint64)
+    return b"".join(raw), off
+
+
+def clean_term(b):
+    """ii_clean_term: the word the index holds for the raw token b (b"" = none)."""
+    b = _term_bytes(b)
+    out = ctypes.create_string_buffer(MAX_WORD)
+    n = lib().ii_clean_term(b, len(b), out)
+    return out.raw[:n]
 
 
 def reducer_letters(r, R):

@@ -17,6 +17,7 @@
 #include "../../include/ii.h"
 #include "ii_kernels.h"
 #include "ii_partial.h"
+#include "ii_query.h"
 #include "ii_reader.h"
 
 
@@ -150,6 +151,17 @@ struct ii_ctx {
     std::vector<hipStream_t> io_st;
     std::vector<uint8_t*> io_buf;
     std::vector<hipEvent_t> io_ev;
+    // term queries (ii_lookup / ii_query): buffers of their own, so a query leaves the index and its text alone
+    DBuf q_arena, q_toff, q_first;                 // cleaned terms, their offsets, first term of every query
+    DBuf q_lex, q_ps, q_df, q_use;                 // per term: lexid, first posting, df, df as its query uses it
+    DBuf q_drv, q_bound, q_tiles, q_tot;           // per query: driver term, candidate segment, work items; totals
+    DBuf q_cand, q_gex, q_ids, q_roff;             // candidates, survivors before every 64th, result ids / offsets
+    std::vector<uint8_t> h_q_arena;
+    std::vector<uint32_t> h_q_toff, h_q_ids;
+    std::vector<uint64_t> h_q_roff;
+    bool q_valid = false;                          // q_roff / q_ids hold the last ii_query's result
+    ii_query_stats qstats{};
+    hipEvent_t ev_q[4] = {};                       // around the lookup / the combine of the last ii_query
     double io_ms = 0;       // host wall time of the last ii_map_files read + upload
     uint64_t io_bytes = 0;
     ii_stats stats;
@@ -856,6 +868,7 @@ extern "C" int ii_open(ii_ctx** out, int device) {
     for (auto& e : c->ev_res) HIPCK(hipEventCreate(&e));
     for (auto& e : c->ev_c0) HIPCK(hipEventCreate(&e));
     for (auto& e : c->ev_dict) HIPCK(hipEventCreate(&e));
+    for (auto& e : c->ev_q) HIPCK(hipEventCreate(&e));
     HIPCK(hipHostMalloc((void**)&c->hbuf, kHbufWords * sizeof(uint64_t), hipHostMallocDefault));
     HIPCK(hipEventCreateWithFlags(&c->ev_rd, hipEventDisableTiming));
     if (grow(c->partial, sizeof(uint64_t) * (2 * kMaxChunks + 1)) ||
@@ -900,7 +913,9 @@ extern "C" void ii_close(ii_ctx* c) {
                    &c->ppieces,  &c->pcnt,   &c->pout,  &c->ploff, &c->chunk_files, &c->pstop, &c->wmap,
                    &c->lexw,     &c->widl,   &c->fbase, &c->pstart_w, &c->pstop_w, &c->mstart, &c->mend,
                    &c->dhist,    &c->lbstat, &c->ticket, &c->pstart_x, &c->msd, &c->tbk, &c->moff,
-                   &c->partial2, &c->rtable2, &c->kept2, &c->drank, &c->g64, &c->shist};
+                   &c->partial2, &c->rtable2, &c->kept2, &c->drank, &c->g64, &c->shist,
+                   &c->q_arena,  &c->q_toff, &c->q_first, &c->q_lex, &c->q_ps, &c->q_df, &c->q_use, &c->q_drv,
+                   &c->q_bound,  &c->q_tiles, &c->q_tot, &c->q_cand, &c->q_gex, &c->q_ids, &c->q_roff};
     for (DBuf* b : all)
         if (b->p) (void)hipFree(b->p);
     for (auto& e : c->ev)
@@ -914,6 +929,8 @@ extern "C" void ii_close(ii_ctx* c) {
     for (auto& e : c->ev_c0)
         if (e) (void)hipEventDestroy(e);
     for (auto& e : c->ev_dict)
+        if (e) (void)hipEventDestroy(e);
+    for (auto& e : c->ev_q)
         if (e) (void)hipEventDestroy(e);
     if (c->ev_rd) (void)hipEventDestroy(c->ev_rd);
     if (c->st2) (void)hipStreamSynchronize(c->st2);
@@ -2273,6 +2290,222 @@ extern "C" int ii_get_stats(ii_ctx* c, ii_stats* o) {
     s.io_ms = c->io_ms;
     s.io_bytes = c->io_bytes;
     *o = s;
+    return II_OK;
+}
+
+// ----------------------------------------------------------------- term queries
+// (kernels: ii_query.h).  Host round trips of one ii_query: two — the plan's
+// totals (candidates and work items, which size the candidate buffer and the
+// combine launch), then the number of result ids, read with the result
+// offsets.  A caller that wants the ids on the host pays the copy of those ids
+// as a third wait, its size being known only then; ii_query_device avoids it.
+// ii_lookup: one.
+extern "C" size_t ii_clean_term(const char* in, size_t n, char out[II_MAX_WORD]) {
+    size_t j = 0;
+    if (!out) return 0;
+    for (size_t i = 0; in && i < n && j < II_MAX_WORD - 1; i++) {  // main.c:105
+        const uint8_t ch = (uint8_t)in[i];
+        if (ch == 0 || host_ws(ch)) break;  // where fscanf("%s") ends a token (main.c:102)
+        if (ch >= 'A' && ch <= 'Z') out[j++] = (char)(ch + 32);   // main.c:106-107
+        else if (ch >= 'a' && ch <= 'z') out[j++] = (char)ch;     // main.c:108-109
+    }
+    out[j] = 0;
+    return j;
+}
+
+static bool offsets_ascend(const uint32_t* off, uint32_t n) {
+    for (uint32_t i = 0; i < n; i++)
+        if (off[i] > off[i + 1]) return false;
+    return true;
+}
+
+static bool index_is_empty(const ii_ctx* c) { return c->T == 0 || c->V == 0 || c->U == 0; }
+
+// Cleans the nterms terms on the host, uploads them and looks them up:
+// q_lex / q_ps / q_df per term, q_tot[QT_FOUND]; q_tot is cleared first.
+static int lookup_terms(ii_ctx* c, const char* terms, const uint32_t* term_off, uint32_t nterms) {
+    c->h_q_arena.clear();
+    c->h_q_toff.resize((size_t)nterms + 1);
+    char w[II_MAX_WORD];
+    for (uint32_t t = 0; t < nterms; t++) {
+        c->h_q_toff[t] = (uint32_t)c->h_q_arena.size();
+        const size_t len = ii_clean_term(terms + term_off[t], term_off[t + 1] - term_off[t], w);
+        c->h_q_arena.insert(c->h_q_arena.end(), w, w + len);
+        if (c->h_q_arena.size() > 0xFFFFFFFFull) return II_ERR_ARG;
+    }
+    c->h_q_toff[nterms] = (uint32_t)c->h_q_arena.size();
+    CK(grow(c->q_arena, std::max<size_t>(c->h_q_arena.size(), 16)));
+    CK(grow(c->q_toff, sizeof(uint32_t) * ((size_t)nterms + 1)));
+    CK(grow(c->q_lex, sizeof(uint32_t) * nterms));
+    CK(grow(c->q_ps, sizeof(uint64_t) * nterms));
+    CK(grow(c->q_df, sizeof(uint32_t) * nterms));
+    CK(grow(c->q_tot, sizeof(uint64_t) * QT_NUM));
+    if (!c->h_q_arena.empty())
+        HIPCK(hipMemcpyAsync(c->q_arena.p, c->h_q_arena.data(), c->h_q_arena.size(), hipMemcpyHostToDevice, c->st));
+    HIPCK(hipMemcpyAsync(c->q_toff.p, c->h_q_toff.data(), sizeof(uint32_t) * ((size_t)nterms + 1),
+                         hipMemcpyHostToDevice, c->st));
+    HIPCK(hipMemsetAsync(c->q_tot.p, 0, sizeof(uint64_t) * QT_NUM, c->st));
+    HIPCK(hipEventRecord(c->ev_q[0], c->st));
+    k_query_lookup<<<grid_for(nterms), kBlock, 0, c->st>>>(
+        c->text, c->nbytes, P_<uint64_t>(c->dkey), P_<uint64_t>(c->lrep), P_<uint32_t>(c->llen),
+        P_<uint64_t>(c->pstart), P_<uint64_t>(c->pstop), (uint32_t)c->V, P_<uint8_t>(c->q_arena),
+        P_<uint32_t>(c->q_toff), nterms, P_<uint32_t>(c->q_lex), P_<uint64_t>(c->q_ps), P_<uint32_t>(c->q_df),
+        P_<uint64_t>(c->q_tot));
+    HIPCK(hipGetLastError());
+    HIPCK(hipEventRecord(c->ev_q[1], c->st));
+    return II_OK;
+}
+
+extern "C" int ii_lookup(ii_ctx* c, const char* terms, const uint32_t* term_off, uint32_t nterms, uint32_t* df_out) {
+    if (!c) return II_ERR_ARG;
+    if (nterms && (!terms || !term_off || !df_out)) return II_ERR_ARG;
+    if (nterms && !offsets_ascend(term_off, nterms)) return II_ERR_ARG;
+    if (!c->have_pairs) return II_ERR_STATE;
+    LIVE_OR_FAIL();
+    if (nterms == 0) return II_OK;
+    if (index_is_empty(c)) {
+        memset(df_out, 0, sizeof(uint32_t) * nterms);
+        return II_OK;
+    }
+    HIPCK(hipSetDevice(c->dev));
+    CK(lookup_terms(c, terms, term_off, nterms));
+    HIPCK(hipMemcpyAsync(df_out, c->q_df.p, sizeof(uint32_t) * nterms, hipMemcpyDeviceToHost, c->st));
+    HIPCK(hipStreamSynchronize(c->st));
+    return II_OK;
+}
+
+// II_QUERY_TILE=<power of two >= 64> (test knob, read per call): postings per work item
+static int query_tile_log2() {
+    int lg = bitlen(kQueryTile) - 1;
+    if (const char* e = getenv("II_QUERY_TILE")) {
+        const long v = atol(e);
+        if (v >= 64 && v <= (1l << 30) && (v & (v - 1)) == 0) lg = bitlen((uint64_t)v) - 1;
+    }
+    return lg;
+}
+
+extern "C" int ii_query(ii_ctx* c, const char* terms, const uint32_t* term_off, const uint32_t* query_first,
+                        uint32_t nqueries, int op, const uint64_t** res_off, const uint32_t** res_ids) {
+    if (!c) return II_ERR_ARG;
+    if (op != II_Q_AND && op != II_Q_OR) return II_ERR_ARG;
+    if ((res_off == nullptr) != (res_ids == nullptr)) return II_ERR_ARG;
+    if (nqueries && !query_first) return II_ERR_ARG;
+    if (nqueries && !offsets_ascend(query_first, nqueries)) return II_ERR_ARG;
+    for (uint32_t q = 0; q < nqueries; q++)
+        if (query_first[q + 1] - query_first[q] > II_MAX_QUERY_TERMS) return II_ERR_ARG;
+    const uint32_t nterms = nqueries ? query_first[nqueries] : 0;
+    if (nterms && (!terms || !term_off)) return II_ERR_ARG;
+    if (nterms && !offsets_ascend(term_off, nterms)) return II_ERR_ARG;
+    if (!c->have_pairs) return II_ERR_STATE;
+    LIVE_OR_FAIL();
+    HIPCK(hipSetDevice(c->dev));
+    const double t0 = now_ms();
+    const bool to_host = res_off != nullptr;
+    c->q_valid = false;
+    ii_query_stats qs;
+    memset(&qs, 0, sizeof(qs));
+    qs.queries = nqueries;
+    qs.terms = nterms;
+    CK(grow(c->q_roff, sizeof(uint64_t) * ((size_t)nqueries + 1)));
+    CK(grow(c->q_ids, sizeof(uint32_t) * 4));
+    uint64_t nout = 0;
+    bool timed = false;
+    if (nqueries == 0 || nterms == 0 || index_is_empty(c)) {  // every result is empty
+        HIPCK(hipMemsetAsync(c->q_roff.p, 0, sizeof(uint64_t) * ((size_t)nqueries + 1), c->st));
+        HIPCK(hipStreamSynchronize(c->st));
+        if (to_host) c->h_q_roff.assign((size_t)nqueries + 1, 0);
+    } else {
+        CK(lookup_terms(c, terms, term_off, nterms));
+        const int tlg = query_tile_log2();
+        CK(grow(c->q_first, sizeof(uint32_t) * ((size_t)nqueries + 1)));
+        CK(grow(c->q_use, sizeof(uint32_t) * nterms));
+        CK(grow(c->q_drv, sizeof(uint32_t) * nqueries));
+        CK(grow(c->q_bound, sizeof(uint64_t) * nqueries));
+        CK(grow(c->q_tiles, sizeof(uint64_t) * nqueries));
+        // (query_first is the caller's memory: the copy is consumed before this call returns)
+        HIPCK(hipMemcpyAsync(c->q_first.p, query_first, sizeof(uint32_t) * ((size_t)nqueries + 1), hipMemcpyHostToDevice,
+                             c->st));
+        uint64_t* tot = P_<uint64_t>(c->q_tot);
+        uint64_t* boff = P_<uint64_t>(c->q_bound);
+        uint64_t* istart = P_<uint64_t>(c->q_tiles);
+        k_query_plan<<<grid_for(nqueries), kBlock, 0, c->st>>>(P_<uint32_t>(c->q_first), nqueries, op == II_Q_OR,
+                                                              P_<uint32_t>(c->q_lex), P_<uint32_t>(c->q_df),
+                                                              P_<uint32_t>(c->q_use), P_<uint32_t>(c->q_drv), boff,
+                                                              istart, tlg, tot);
+        HIPCK(hipGetLastError());
+        CK(run_scan(c, OpInPlace{boff}, nqueries, tot + QT_BOUND));
+        CK(run_scan(c, OpInPlace{istart}, nqueries, tot + QT_ITEMS));
+        uint64_t h[QT_NUM];
+        CK(read_u64(c, tot, h, QT_NUM));  // round trip 1
+        const uint64_t B = h[QT_BOUND], nitems = h[QT_ITEMS];
+        qs.terms_found = (uint32_t)h[QT_FOUND];
+        qs.postings_read = h[QT_POSTINGS];
+        const uint64_t nblocks = (nitems + kWG - 1) / kWG;
+        if (nblocks >= (1ull << 31)) return II_ERR_NOMEM;
+        CK(grow(c->q_cand, sizeof(uint32_t) * std::max<uint64_t>(B, 4)));
+        CK(grow(c->q_gex, sizeof(uint64_t) * (B / kQueryPad + 1)));
+        CK(grow(c->q_ids, sizeof(uint32_t) * std::max<uint64_t>(B, 4)));
+        uint32_t* cand = P_<uint32_t>(c->q_cand);
+        HIPCK(hipEventRecord(c->ev_q[2], c->st));
+        if (nitems) {
+            const uint32_t* qf = P_<uint32_t>(c->q_first);
+            const uint64_t* tps = P_<uint64_t>(c->q_ps);
+            const uint32_t* use = P_<uint32_t>(c->q_use);
+            if (op == II_Q_OR) {  // (dropped repeats write nothing, nor does anyone write the padding)
+                HIPCK(hipMemsetAsync(cand, 0, sizeof(uint32_t) * B, c->st));
+                (c->pairs32 ? k_query_or<true> : k_query_or<false>)<<<(uint32_t)nblocks, kBlock, 0, c->st>>>(
+                    c->uniq.p, qf, tps, use, istart, boff, nqueries, nitems, tlg, cand);
+            } else {
+                (c->pairs32 ? k_query_and<true> : k_query_and<false>)<<<(uint32_t)nblocks, kBlock, 0, c->st>>>(
+                    c->uniq.p, qf, tps, use, P_<uint32_t>(c->q_drv), istart, boff, nqueries, nitems, tlg, cand);
+            }
+            HIPCK(hipGetLastError());
+        }
+        CK(run_scan(c, OpQueryCompact{cand, P_<uint32_t>(c->q_ids), P_<uint64_t>(c->q_gex)}, B, tot + QT_OUT));
+        k_query_off<<<grid_for((uint64_t)nqueries + 1), kBlock, 0, c->st>>>(boff, nqueries, P_<uint64_t>(c->q_gex), tot,
+                                                                           P_<uint64_t>(c->q_roff));
+        HIPCK(hipGetLastError());
+        HIPCK(hipEventRecord(c->ev_q[3], c->st));
+        if (to_host) {
+            c->h_q_roff.resize((size_t)nqueries + 1);
+            HIPCK(hipMemcpyAsync(c->h_q_roff.data(), c->q_roff.p, sizeof(uint64_t) * ((size_t)nqueries + 1),
+                                 hipMemcpyDeviceToHost, c->st));
+        }
+        CK(read_u64(c, tot + QT_OUT, &nout));  // round trip 2
+        timed = true;
+    }
+    if (to_host) {
+        c->h_q_ids.resize(std::max<uint64_t>(nout, 1));
+        if (nout) {
+            HIPCK(hipMemcpyAsync(c->h_q_ids.data(), c->q_ids.p, sizeof(uint32_t) * nout, hipMemcpyDeviceToHost, c->st));
+            HIPCK(hipStreamSynchronize(c->st));
+        }
+        *res_off = c->h_q_roff.data();
+        *res_ids = c->h_q_ids.data();
+    }
+    qs.ids_out = nout;
+    if (timed) {
+        qs.ms_lookup = ev_ms(c->ev_q[0], c->ev_q[1]);
+        qs.ms_combine = ev_ms(c->ev_q[2], c->ev_q[3]);
+    }
+    qs.ms_total = now_ms() - t0;
+    c->qstats = qs;
+    c->q_valid = true;
+    return II_OK;
+}
+
+extern "C" int ii_query_device(ii_ctx* c, const uint64_t** d_res_off, const uint32_t** d_res_ids) {
+    if (!c || !d_res_off || !d_res_ids) return II_ERR_ARG;
+    if (!c->q_valid) return II_ERR_STATE;
+    *d_res_off = P_<uint64_t>(c->q_roff);
+    *d_res_ids = P_<uint32_t>(c->q_ids);
+    return II_OK;
+}
+
+extern "C" int ii_get_query_stats(ii_ctx* c, ii_query_stats* out) {
+    if (!c || !out) return II_ERR_ARG;
+    if (!c->q_valid) return II_ERR_STATE;
+    *out = c->qstats;
     return II_OK;
 }
 
