@@ -19,6 +19,7 @@
 #include "ii_partial.h"
 #include "ii_query.h"
 #include "ii_reader.h"
+#include "ii_sortplan.h"
 
 
 using namespace ii;
@@ -31,6 +32,17 @@ struct DBuf {
 };
 
 constexpr int kMaxTimedPasses = 16;
+
+// What ii_get_stats reports about the token sort of the context's last local reduce: assigned once, at
+// the end of local_reduce.  A map zeroes c0_bytes and T_sorted; an import (which maps, but sorts no
+// tokens) leaves the other fields at the values of the last local reduce.
+struct SortStats {
+    bool sort_packed = false;      // it ran in the packed form (token_sort_packed)
+    int sort_W = 0, sort_F = 0;    // its key / id bits
+    uint64_t sort_hist_bytes = 0;  // its bucket-histogram reads
+    uint64_t c0_bytes = 0;         // k_sort0_compact's algorithmic bytes (records read + kept records written)
+    uint64_t T_sorted = 0;         // records left after the first pass's dedup
+};
 
 }  // namespace
 
@@ -55,9 +67,6 @@ struct ii_ctx {
     // the mapped files' id0s are fid_off, fid_off + 1, ... (a caller's id range; ii_partition's size-sorted
     // shares are not): K3 adds fid_off to K1's shard-local file index instead of gathering fid[index]
     bool fid_affine = true;
-    // the packed token sort's first pass maps shard-local file indices to id0s (local_reduce):
-    // the sorted records then carry id0s, and K3 gathers nothing
-    const uint32_t* s0_fmap = nullptr;
     uint32_t fid_off = 0;
     IdDigitsTh dth{};       // K3's posting bytes by file index (pair_bytes)
     DBuf fstart, fid;
@@ -116,7 +125,6 @@ struct ii_ctx {
                               // (or the owner's import) must fail
     uint32_t retries = 0;
     bool mapped = false, have_pairs = false, reduced = false;
-    uint64_t* rec_sorted = nullptr;
     uint32_t* ord = nullptr;
     uint64_t hist[II_ALPHABET] = {0};
     uint64_t h_letter_off[II_ALPHABET + 1] = {0};
@@ -129,18 +137,10 @@ struct ii_ctx {
     hipEvent_t ev_sc[2 * kMaxTimedPasses] = {};
     uint64_t sc_bytes[kMaxTimedPasses] = {0};  // algorithmic bytes of each timed scatter launch
     int n_sc = 0;
-    uint64_t T_sorted = 0;  // records left after the pass-0 dedup
     hipEvent_t ev_c0[2] = {};  // around k_sort0_compact
     hipEvent_t ev_dict[2] = {};  // the dictionary's lexicographic part on st2: may start / done
-    uint64_t c0_bytes = 0;     // its algorithmic bytes (records read + kept records written)
-    bool sort_packed = false;  // the last token sort ran in the packed form (run_sort_packed)
-    int sort_W = 0, sort_F = 0;  // its key / file-index bits
-    uint64_t sort_hist_bytes = 0;  // its bucket-histogram reads
-    // packed form: the sorted u32 records' layout (bucket geometry in msd, bits), for K3
-    uint32_t pk_nb = 0, pk_ntb = 0;
-    uint64_t pk_ncap = 0;  // u32 records K3 may load (the padded layout's extent)
+    SortStats last_sort;   // what ii_get_stats reports about the last token sort
     int ncu = 256;         // compute units (persistent launches)
-    int pk_F = 0, pk_L = 0;
     uint64_t n_pending = 0; // tokens K1b left to K1c
     bool deep_probe = false; // K1b's DeepProbe: most distinct words of the context's last reduce lived in the big table
     uint32_t rec_lbits = 0;  // the last map's narrow records: slot << rec_lbits | file - the chunk's first file
@@ -253,7 +253,6 @@ static inline double now_ms() {
     clock_gettime(CLOCK_MONOTONIC, &ts);
     return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6;
 }
-static inline int bitlen(uint64_t v) { return v ? 64 - __builtin_clzll(v) : 0; }
 // bytes the packed token sort's u32 layout of n records may take (every bucket padded to whole tiles)
 // (n + (kMsdMax + 1) tiles: every bucket's last tile padded, plus the launch's whole tiles, k_onesweep_seg ncap)
 static inline size_t packed_bytes(uint64_t n) { return sizeof(uint32_t) * (n + (uint64_t)(kMsdMax + 1) * kSweepTile); }
@@ -360,67 +359,78 @@ static int lookback_pass(ii_ctx* c, uint64_t entries) {
     return II_OK;
 }
 
-// The first pass of a token sort (k_sort0_compact) over the K1 records *k into
-// *k2: one workgroup per `group` K1b chunks (at most kMaxChunks workgroups),
-// one table column each.
-struct S0Geom {
-    uint64_t group, ncol;  // ncol: workgroups = table columns = the scatter's workgroups
-};
-static int s0_geometry(ii_ctx* c, S0Geom* g) {
-    const uint64_t nch_in = c->nch_map;
-    g->group = (nch_in + kMaxChunks - 1) / kMaxChunks;
-    if (nch_in == 0 || g->group > kCMaxGroup) return II_ERR_NOMEM;
-    g->ncol = (nch_in + g->group - 1) / g->group;
-    return II_OK;
+// k_sort0_compact's instances by the plan's [wid][wide][hashd][the map wrote multi-file narrow chunks]
+#define II_S0(w, d, h) {k_sort0_compact<w, d, h, false>, k_sort0_compact<w, d, h, true>}
+static constexpr decltype(&k_sort0_compact<false, false, false, false>) kSort0[2][2][2][2] = {
+    {{II_S0(false, false, false), II_S0(false, false, true)}, {II_S0(false, true, false), II_S0(false, true, true)}},
+    {{II_S0(true, false, false), II_S0(true, false, true)}, {II_S0(true, true, false), II_S0(true, true, true)}}};
+#undef II_S0
+
+// The first pass of both token-sort forms, over the K1 records k into k2: k_sort0_compact (one workgroup per
+// `group` K1b chunks; *ncol workgroups = table columns = the scatter's workgroups) drops repeated (hot word,
+// file) records, maps slots to keys (and file indices to id0s: IdSource::MappedInSort0), compacts each
+// workgroup's range and counts the digit (shift, dmask) per column of c->rtable (`rows` digit rows; kept ranges
+// in c->kept); then the table scan (totals[4, 9): what sort0_counts reads).  shift1 / shift2 / dhist: the later
+// digits counted for the u64 form's onesweep passes (the packed form, whose record-set instances count none: 0, 0, null).
+static int sort0_pass(ii_ctx* c, const TokenSortPlan& p, const uint64_t* k, uint64_t* k2, int shift, uint32_t dmask,
+                      uint32_t rows, int shift1, int shift2, uint64_t* dhist, uint64_t* ncol) {
+    const uint64_t group = (c->nch_map + kMaxChunks - 1) / kMaxChunks;  // (at most kMaxChunks workgroups)
+    if (c->nch_map == 0 || group > kCMaxGroup) return II_ERR_NOMEM;
+    *ncol = (c->nch_map + group - 1) / group;
+    CK(grow(c->rtable, sizeof(uint64_t) * rows * kMaxChunks));
+    CK(grow(c->kept, sizeof(uint64_t) * 2 * kMaxChunks));
+    uint64_t* table = P_<uint64_t>(c->rtable);
+    HIPCK(hipEventRecord(c->ev_c0[0], c->st));
+    kSort0[p.wid][p.wide][p.hashd][c->rec_lbits != 0]<<<(uint32_t)*ncol, kCBlock, 0, c->st>>>(
+        k, P_<uint64_t>(c->chunk_cnt), (uint32_t)c->nch_map, (uint32_t)group, c->rec_cap, shift, dmask, (uint32_t)*ncol,
+        table, P_<uint32_t>(p.wid ? c->wmap : c->remap), k2, P_<uint64_t>(c->kept), shift1, shift2, dhist,
+        P_<uint32_t>(c->chunk_files), P_<unsigned long long>(c->totals) + 8, c->rec_lbits,
+        p.ids == IdSource::MappedInSort0 ? P_<uint32_t>(c->fid) : nullptr);
+    HIPCK(hipEventRecord(c->ev_c0[1], c->st));
+    return run_scan(c, OpInPlace{table}, (uint64_t)rows * *ncol, P_<uint64_t>(c->totals) + 4);
 }
-// The first pass's algorithmic bytes: 4 B per record of a narrow chunk (K1b
-// wrote u32 word slots there; two lanes share each 8-B load), 8 B per other
-// record, 8 B per kept record written.
-static uint64_t s0_bytes(uint64_t n_in, uint64_t n_narrow, uint64_t n_kept) {
-    n_narrow = std::min(n_narrow, n_in);
-    return 4 * n_narrow + 8 * (n_in - n_narrow) + 8 * n_kept;
-}
-template <bool kWid, bool kWideD, bool kHashD = false>
-static void sort0_inst(ii_ctx* c, const S0Geom& g, const uint64_t* k, uint64_t* k2, int shift, uint32_t dmask,
-                       uint64_t* table, const uint32_t* remap, uint64_t* kept, int shift1, int shift2, uint64_t* dhist) {
-    (c->rec_lbits ? k_sort0_compact<kWid, kWideD, kHashD, true> : k_sort0_compact<kWid, kWideD, kHashD, false>)
-        <<<(uint32_t)g.ncol, kCBlock, 0, c->st>>>(
-        k, P_<uint64_t>(c->chunk_cnt), (uint32_t)c->nch_map, (uint32_t)g.group, c->rec_cap, shift, dmask,
-        (uint32_t)g.ncol, table, remap, k2, kept, shift1, shift2, dhist, P_<uint32_t>(c->chunk_files),
-        P_<unsigned long long>(c->totals) + 8, c->rec_lbits, c->s0_fmap);
-}
-static void launch_sort0(ii_ctx* c, const S0Geom& g, bool wid, const uint64_t* k, uint64_t* k2, int shift,
-                         uint32_t dmask, uint64_t* table, const uint32_t* remap, uint64_t* kept, int shift1, int shift2,
-                         uint64_t* dhist, bool wide = false, bool hashd = false) {
-    if (hashd) {  // (the packed sort only: no later-digit counts)
-        if (wid && wide) sort0_inst<true, true, true>(c, g, k, k2, shift, dmask, table, remap, kept, 0, 0, nullptr);
-        else if (wid) sort0_inst<true, false, true>(c, g, k, k2, shift, dmask, table, remap, kept, 0, 0, nullptr);
-        else if (wide) sort0_inst<false, true, true>(c, g, k, k2, shift, dmask, table, remap, kept, 0, 0, nullptr);
-        else sort0_inst<false, false, true>(c, g, k, k2, shift, dmask, table, remap, kept, 0, 0, nullptr);
-        return;
-    }
-    if (wid && wide) sort0_inst<true, true>(c, g, k, k2, shift, dmask, table, remap, kept, shift1, shift2, dhist);
-    else if (wid) sort0_inst<true, false>(c, g, k, k2, shift, dmask, table, remap, kept, shift1, shift2, dhist);
-    else if (wide) sort0_inst<false, true>(c, g, k, k2, shift, dmask, table, remap, kept, shift1, shift2, dhist);
-    else sort0_inst<false, false>(c, g, k, k2, shift, dmask, table, remap, kept, shift1, shift2, dhist);
+// The first pass's counts t47 = totals[4, 9): the records kept (returned), the exact wid range (k_count_hot wrote
+// the occupied hot slots to totals[7]) and the pass's algorithmic bytes: 4 B per record of a narrow chunk (K1b
+// wrote u32 word slots there; two lanes share each 8-B load), 8 B per other record, 8 B per kept record written.
+static uint64_t sort0_counts(ii_ctx* c, const TokenSortPlan& p, const uint64_t t47[5], uint64_t n_in, uint64_t* c0_bytes) {
+    if (p.wid) c->NW = kHotSlots + (c->V - (t47[3] & 0xFFFFFFFFull));
+    *c0_bytes = 4 * std::min(t47[4], n_in) + 8 * (n_in - std::min(t47[4], n_in)) + 8 * t47[0];
+    return t47[0];
 }
 
 // test knobs: raise error bits on the device (stream-ordered)
 __global__ void k_set_bits(uint64_t* p, unsigned long long bits) { atomicOr((unsigned long long*)p, bits); }
 
-// Stable LSD radix sort of n u64 keys (optionally with u32 values) on bits
-// [lo, hi).  On return *k / *v point at the sorted arrays (buffers swap).
-// With remap0 (token sort only, no values) the first pass is k_sort0_compact:
-// it drops repeated (hot word, file) records, maps slots to lexicographic ids
-// and compacts each workgroup's range into *k2; that pass's scatter reads the
-// kept ranges back into *k, and the remaining passes run over the kept
-// records only.  *n_out receives the number of records kept.
-// The same sort without a first pass, by onesweep passes: one read of the
-// keys counts every pass's digits (k_hist_passes), then one launch per pass
-// (decoupled look-back: no per-pass histogram, table scan or scan launches).
-// The dictionary's key / index sorts of the exchange path and the owner's
-// import ran 8 x (histogram + scan + scatter) small launches before.  Main
-// stream only: the look-back entries and the tile ticket are the token sort's.
+// One onesweep pass (decoupled look-back) of n keys, and their values, on the digit (shift, db) whose
+// bases are `bases`; *k / *v swap.  timed: events and algorithmic bytes as hist_passes'.
+static int sweep_pass(ii_ctx* c, uint64_t** k, uint64_t** k2, uint32_t** v, uint32_t** v2, uint64_t n, int shift, int db,
+                      const uint64_t* bases, bool timed, int* passes) {
+    const uint64_t ntiles = (n + kSweepTile - 1) / kSweepTile;
+    const bool ev = timed && c->n_sc < kMaxTimedPasses;
+    CK(lookback_pass(c, ntiles * kRadix));
+    if (ev) HIPCK(hipEventRecord(c->ev_sc[2 * c->n_sc], c->st));
+    if (v)
+        k_onesweep<kSweepThreads, kSweepItems, 2, true><<<(uint32_t)ntiles, kSweepThreads, 0, c->st>>>(
+            *k, *k2, n, shift, db, bases, P_<uint64_t>(c->lbstat), P_<uint32_t>(c->ticket), c->lb_epoch,
+            P_<unsigned long long>(c->counters) + C_OVERFLOW, *v, *v2);
+    else
+        k_onesweep<kSweepThreads, kSweepItems><<<(uint32_t)ntiles, kSweepThreads, 0, c->st>>>(
+            *k, *k2, n, shift, db, bases, P_<uint64_t>(c->lbstat), P_<uint32_t>(c->ticket), c->lb_epoch,
+            P_<unsigned long long>(c->counters) + C_OVERFLOW, nullptr, nullptr);
+    if (ev) {
+        HIPCK(hipEventRecord(c->ev_sc[2 * c->n_sc + 1], c->st));
+        c->sc_bytes[c->n_sc++] = 16 * n;
+    }
+    HIPCK(hipGetLastError());
+    std::swap(*k, *k2);
+    if (v) std::swap(*v, *v2);
+    if (passes) (*passes)++;
+    return II_OK;
+}
+
+// run_sort by onesweep passes: one read of the keys counts every pass's digits (k_hist_passes), then
+// one launch per pass (decoupled look-back: no per-pass histogram, table scan or scan launches).
+// Main stream only: the look-back entries and the tile ticket are the token sort's.
 static int run_sort_sweep(ii_ctx* c, uint64_t** k, uint64_t** k2, uint32_t** v, uint32_t** v2, uint64_t n, int lo,
                           int hi, int* passes) {
     const int npass = (hi - lo + kRadixBits - 1) / kRadixBits;
@@ -434,201 +444,69 @@ static int run_sort_sweep(ii_ctx* c, uint64_t** k, uint64_t** k2, uint32_t** v, 
         *k, n, lo, hi, bits, npass, counts);
     k_digit_bases<<<npass, kRadix, 0, c->st>>>(counts, bases);
     HIPCK(hipGetLastError());
-    const uint64_t ntiles = (n + kSweepTile - 1) / kSweepTile;
-    for (int p = 0; p < npass; p++) {
-        const int shift = lo + p * bits, db = std::min(bits, hi - shift);
-        CK(lookback_pass(c, ntiles * kRadix));
-        if (v)
-            k_onesweep<kSweepThreads, kSweepItems, 2, true><<<(uint32_t)ntiles, kSweepThreads, 0, c->st>>>(
-                *k, *k2, n, shift, db, bases + (uint64_t)p * kRadix, P_<uint64_t>(c->lbstat), P_<uint32_t>(c->ticket),
-                c->lb_epoch, P_<unsigned long long>(c->counters) + C_OVERFLOW, *v, *v2);
-        else
-            k_onesweep<kSweepThreads, kSweepItems><<<(uint32_t)ntiles, kSweepThreads, 0, c->st>>>(
-                *k, *k2, n, shift, db, bases + (uint64_t)p * kRadix, P_<uint64_t>(c->lbstat), P_<uint32_t>(c->ticket),
-                c->lb_epoch, P_<unsigned long long>(c->counters) + C_OVERFLOW, nullptr, nullptr);
-        HIPCK(hipGetLastError());
-        std::swap(*k, *k2);
-        if (v) std::swap(*v, *v2);
-        if (passes) (*passes)++;
-    }
+    for (int p = 0; p < npass; p++)
+        CK(sweep_pass(c, k, k2, v, v2, n, lo + p * bits, std::min(bits, hi - lo - p * bits), bases + (uint64_t)p * kRadix,
+                      false, passes));
     if (c->test_lb_timeout == 3 && v) k_set_bits<<<1, 1, 0, c->st>>>(P_<uint64_t>(c->counters) + C_OVERFLOW, kLbTimeout);
     return II_OK;
 }
 
-// sweep_ok = false keeps the histogram + scan + scatter passes, which cannot time out: for sorts whose
-// values later kernels use as indices before the host can read the look-back flag (a onesweep pass that
-// flagged kLbTimeout leaves slots of its output unwritten — stale values, out-of-range indices).
-static int run_sort(ii_ctx* c, uint64_t** k, uint64_t** k2, uint32_t** v, uint32_t** v2, uint64_t n, int lo, int hi,
-                    bool timed, int* passes, const uint32_t* remap0 = nullptr, uint64_t* n_out = nullptr,
-                    bool wid = false, bool sweep_ok = true) {
-    if (passes) *passes = 0;
-    if (n_out) *n_out = n;
-    if (hi <= lo || (n <= 1 && !remap0)) return II_OK;
-    if (remap0 && v) return II_ERR_INTERNAL;
-    if (!remap0 && sweep_ok && !c->on_side && !timed && !getenv("II_SORT_NO_SWEEP")) return run_sort_sweep(c, k, k2, v, v2, n, lo, hi, passes);
-    // first pass over K1's records: one workgroup (or pair) per `group` K1b chunks
-    S0Geom s0{};
-    if (remap0) CK(s0_geometry(c, &s0));
-    uint64_t nch = 0, chunk = 0;
-    auto regrid = [&](uint64_t m, uint64_t tile) {
-        nch = std::min<uint64_t>(kMaxChunks, (m + tile - 1) / tile);
-        chunk = ((m + nch - 1) / nch + tile - 1) / tile * tile;
-        nch = (m + chunk - 1) / chunk;
-    };
-    if (remap0) {
-        nch = s0.ncol;
-        chunk = 0;
-    } else {
-        regrid(n, kSortTile);
-    }
-    CK(grow(c->rtable, sizeof(uint64_t) * kRadix * kMaxChunks));
-    CK(grow(c->kept, sizeof(uint64_t) * 2 * kMaxChunks));
-    uint64_t* table = P_<uint64_t>(c->rtable);
-    uint64_t* kept = P_<uint64_t>(c->kept);
-    const bool kv = v != nullptr;
-    uint64_t* totals = P_<uint64_t>(c->totals);
-    // even digit widths: the fewest passes of <= kRadixBits bits, each as narrow
-    // as that allows (fewer buckets -> longer output runs per tile)
-    const int npass = (hi - lo + kRadixBits - 1) / kRadixBits;
-    const int bits = (hi - lo + npass - 1) / npass;
-    // token sort: the passes after the first are onesweep passes (decoupled
-    // look-back) when their digits fit the histograms k_sort0_compact keeps
-    const bool sweep = remap0 && npass - 1 <= kLaterDigits;
-    uint64_t* dhist = nullptr;
-    if (sweep) {
-        CK(grow(c->dhist, sizeof(uint64_t) * 2 * kLaterDigits * kRadix));
-        dhist = P_<uint64_t>(c->dhist);
-        HIPCK(hipMemsetAsync(dhist, 0, sizeof(uint64_t) * kLaterDigits * kRadix, c->st));
-    }
-    for (int shift = lo, pass = 0; shift < hi; shift += bits, pass++) {
-        const int db = std::min(bits, hi - shift);
-        const uint32_t dmask = (1u << db) - 1u;
-        const bool first0 = remap0 && shift == lo;
-        const bool ev = timed && c->n_sc < kMaxTimedPasses;
-        const uint64_t* src = first0 ? *k2 : *k;
-        uint64_t* dst = first0 ? *k : *k2;
-        if (first0) {
-            if (timed) HIPCK(hipEventRecord(c->ev_c0[0], c->st));
-            launch_sort0(c, s0, wid, *k, *k2, shift, dmask, table, remap0, kept, lo + bits, lo + 2 * bits, dhist);
-            if (timed) HIPCK(hipEventRecord(c->ev_c0[1], c->st));
-            CK(run_scan(c, OpInPlace{table}, (uint64_t)kRadix * nch, totals + 4));
-            if (sweep) k_digit_bases<<<kLaterDigits, kRadix, 0, c->st>>>(dhist, dhist + kLaterDigits * kRadix);
-        } else if (sweep) {
-            // onesweep: one launch per pass, no histogram pass, no table scan
-            const uint64_t ntiles = (n + kSweepTile - 1) / kSweepTile;
-            CK(lookback_pass(c, ntiles * kRadix));
-            if (ev) HIPCK(hipEventRecord(c->ev_sc[2 * c->n_sc], c->st));
-            k_onesweep<kSweepThreads, kSweepItems><<<(uint32_t)ntiles, kSweepThreads, 0, c->st>>>(
-                src, dst, n, shift, db, dhist + kLaterDigits * kRadix + (uint64_t)(pass - 1) * kRadix,
-                P_<uint64_t>(c->lbstat), P_<uint32_t>(c->ticket), c->lb_epoch,
-                P_<unsigned long long>(c->counters) + C_OVERFLOW, nullptr, nullptr);
-            if (ev) {
-                HIPCK(hipEventRecord(c->ev_sc[2 * c->n_sc + 1], c->st));
-                c->sc_bytes[c->n_sc] = 16 * n;
-                c->n_sc++;
-            }
-            HIPCK(hipGetLastError());
-            if (passes) (*passes)++;
-            std::swap(*k, *k2);
-            continue;
-        } else {
-            k_radix_hist<<<(uint32_t)nch, kBlock, 0, c->st>>>(*k, n, chunk, shift, dmask, (uint32_t)nch, table);
-            CK(run_scan(c, OpInPlace{table}, (uint64_t)kRadix * nch, nullptr));
-        }
-        if (ev) HIPCK(hipEventRecord(c->ev_sc[2 * c->n_sc], c->st));
-        if (kv)
-            k_radix_scatter<true><<<(uint32_t)nch, kBlock, 0, c->st>>>(src, dst, *v, *v2, n, chunk, shift, db,
-                                                                      (uint32_t)nch, table, nullptr, nullptr, nullptr,
-                                                                      0, 0u);
-        else
-            k_radix_scatter<false, kScatterThreads, kScatterItems><<<(uint32_t)nch, kScatterThreads, 0, c->st>>>(
-                src, dst, nullptr, nullptr, n, chunk, shift, db, (uint32_t)nch, table, first0 ? kept : nullptr, nullptr,
-                nullptr, 0, 0u);
-        if (ev) {
-            HIPCK(hipEventRecord(c->ev_sc[2 * c->n_sc + 1], c->st));
-            c->n_sc++;
-        }
-        HIPCK(hipGetLastError());
-        if (passes) (*passes)++;
-        if (first0) {  // sorted by the first digit, in *k: the rest runs over the kept records
-            const uint64_t n_in = n;
-            uint64_t t47[5];
-            CK(read_u64(c, totals + 4, t47, 5));
-            n = t47[0];
-            if (wid) {  // exact wid range (k_count_hot wrote the occupied hot slots to totals[7])
-                c->NW = kHotSlots + (c->V - (t47[3] & 0xFFFFFFFFull));
-                hi = std::min(hi, lo + std::max(1, bitlen(c->NW - 1)));
-            }
-            c->c0_bytes = s0_bytes(n_in, t47[4], n);
-            if (ev) c->sc_bytes[c->n_sc - 1] = 16 * n;
-            if (n_out) *n_out = n;
-            if (n <= 1) break;
-            regrid(n, kSortTile);
-        } else {
-            std::swap(*k, *k2);
-            if (kv) std::swap(*v, *v2);
-            if (ev) c->sc_bytes[c->n_sc - 1] = 16 * n + (kv ? 8 * n : 0);
-        }
-    }
-    return II_OK;
-}
-
-// *p |= bits (one thread; the II_TEST_LB_TIMEOUT test knob)
-
-// Stable LSD radix sort of n u32 keys on bits [0, bits): *k / *k2 ping-pong,
-// on return *k holds the sorted keys (the owner's merged pairs when lexid and
-// id0 fit one u32, ii_import).
-static int run_sort32(ii_ctx* c, uint32_t** k, uint32_t** k2, uint64_t n, int bits, int* passes) {
-    *passes = 0;
-    if (n <= 1 || bits <= 0) return II_OK;
-    CK(grow(c->rtable, sizeof(uint64_t) * kRadix * kMaxChunks));
-    uint64_t* table = P_<uint64_t>(c->rtable);
+// Histogram + scan + scatter passes over `bits`-bit digits of [lo, hi) of u64 keys (optionally with
+// u32 values) or u32 keys: they cannot time out.  timed: events around every scatter launch and its
+// algorithmic bytes (ev_sc / sc_bytes, ii_get_stats).
+template <class K>
+static int hist_passes(ii_ctx* c, K** k, K** k2, uint32_t** v, uint32_t** v2, uint64_t n, int lo, int hi, int bits,
+                       bool timed, int* passes) {
     uint64_t nch = std::min<uint64_t>(kMaxChunks, (n + kSortTile - 1) / kSortTile);
     const uint64_t chunk = ((n + nch - 1) / nch + kSortTile - 1) / kSortTile * kSortTile;
     nch = (n + chunk - 1) / chunk;
-    const int npass = (bits + kRadixBits - 1) / kRadixBits, db = (bits + npass - 1) / npass;
-    for (int shift = 0; shift < bits; shift += db) {
-        const int w = std::min(db, bits - shift);
-        const uint32_t dmask = (1u << w) - 1u;
-        k_radix_hist<uint32_t><<<(uint32_t)nch, kBlock, 0, c->st>>>(*k, n, chunk, shift, dmask, (uint32_t)nch, table);
+    CK(grow(c->rtable, sizeof(uint64_t) * kRadix * kMaxChunks));
+    uint64_t* table = P_<uint64_t>(c->rtable);
+    for (int shift = lo; shift < hi; shift += bits) {
+        const int db = std::min(bits, hi - shift);
+        const bool ev = timed && c->n_sc < kMaxTimedPasses;
+        k_radix_hist<K><<<(uint32_t)nch, kBlock, 0, c->st>>>(*k, n, chunk, shift, (1u << db) - 1u, (uint32_t)nch, table);
         CK(run_scan(c, OpInPlace{table}, (uint64_t)kRadix * nch, nullptr));
-        k_radix_scatter<false, kScatterThreads, kScatterItems, false, uint32_t>
-            <<<(uint32_t)nch, kScatterThreads, 0, c->st>>>(*k, *k2, nullptr, nullptr, n, chunk, shift, w, (uint32_t)nch,
-                                                           table, nullptr, nullptr, nullptr, 0, 0u);
+        if (ev) HIPCK(hipEventRecord(c->ev_sc[2 * c->n_sc], c->st));
+        if constexpr (sizeof(K) == 8)  // (values go with u64 keys only)
+            if (v)
+                k_radix_scatter<true><<<(uint32_t)nch, kBlock, 0, c->st>>>(
+                    *k, *k2, *v, *v2, n, chunk, shift, db, (uint32_t)nch, table, nullptr, nullptr, nullptr, 0, 0u);
+        if (!v)
+            k_radix_scatter<false, kScatterThreads, kScatterItems, false, K><<<(uint32_t)nch, kScatterThreads, 0, c->st>>>(
+                *k, *k2, nullptr, nullptr, n, chunk, shift, db, (uint32_t)nch, table, nullptr, nullptr, nullptr, 0, 0u);
+        if (ev) {
+            HIPCK(hipEventRecord(c->ev_sc[2 * c->n_sc + 1], c->st));
+            c->sc_bytes[c->n_sc++] = 16 * n + (v ? 8 * n : 0);
+        }
         HIPCK(hipGetLastError());
+        if (passes) (*passes)++;
         std::swap(*k, *k2);
-        (*passes)++;
+        if (v) std::swap(*v, *v2);
     }
     return II_OK;
 }
 
-// Packed token sort (ii_prims.h, "Packed token sort"): the top digit m of a
-// W-bit key when the other W - m key bits and the F id bits fit a u32 and
-// leave two LSD passes of <= kRadixBits bits; 0 = not packable.  Top digits
-// of up to kMsdMaxBits bits (k_msd_scatter_wide past kRadixBits).
-// II_PACKED_M=<m> (test knob): at least m top bits, so that small inputs reach
-// the wide split.
-static int packed_top_bits(int W, int F) {
-    if (getenv("II_PACKED_SORT") && !strcmp(getenv("II_PACKED_SORT"), "0")) return 0;
-    const char* fm = getenv("II_PACKED_M");
-    const int m = std::max({7, W + F - 32, fm ? atoi(fm) : 0});
-    const int L = W - m;
-    return (m <= kMsdMaxBits && L >= 2 && L <= 2 * kRadixBits) ? m : 0;
-}
-
-// The first pass's dedup for the packed sort: the record set (kHashD) when the
-// files average fewer than kHashDedupTokens tokens (configs[4]'s small-file
-// shares: 3.9·10^3), the epoch bitmap otherwise (config3: 1.4·10^5 per file,
-// more distinct pairs per file than the set holds).  II_S0_DEDUP=set|bitmap
-// (test and A/B knob) forces one.
-constexpr uint64_t kHashDedupTokens = 16384;
-// files at which the first pass maps file indices to id0s (local_reduce; a 256 KiB fmap)
-constexpr uint32_t kS0FmapFiles = 65536;
-static bool dedup_by_set(const ii_ctx* c, uint64_t n) {
-    const char* e = getenv("II_S0_DEDUP");
-    if (e && !strcmp(e, "set")) return true;
-    if (e && !strcmp(e, "bitmap")) return false;
-    return c->nfiles && n < kHashDedupTokens * (uint64_t)c->nfiles;
+struct SortOpts {
+    // onesweep passes allowed (u64 keys, main stream, untimed).  false keeps the histogram passes, which
+    // cannot time out: for sorts whose values later kernels use as indices before the host can read the
+    // look-back flag (a onesweep pass that flagged kLbTimeout leaves slots of its output unwritten —
+    // stale values, out-of-range indices), and for II_SORT_NO_SWEEP
+    bool sweep = false, timed = false;  // timed: hist_passes' events
+    int* passes = nullptr;              // receives the passes run
+};
+// Stable LSD radix sort of n u64 keys (optionally with u32 values) or u32 keys on bits [lo, hi), in the
+// fewest passes of even digit widths <= kRadixBits (fewer buckets -> longer output runs per tile).
+// On return *k / *v point at the sorted arrays (buffers swap).
+template <class K>
+static int run_sort(ii_ctx* c, K** k, K** k2, uint32_t** v, uint32_t** v2, uint64_t n, int lo, int hi,
+                    const SortOpts& o) {
+    if (o.passes) *o.passes = 0;
+    if (hi <= lo || n <= 1) return II_OK;
+    if constexpr (sizeof(K) == 8)
+        if (o.sweep && !c->on_side && !o.timed) return run_sort_sweep(c, k, k2, v, v2, n, lo, hi, o.passes);
+    const int npass = (hi - lo + kRadixBits - 1) / kRadixBits;
+    return hist_passes(c, k, k2, v, v2, n, lo, hi, (hi - lo + npass - 1) / npass, o.timed, o.passes);
 }
 
 // The packed sort's bucket geometry and LSD digit counts in c->msd (sized for
@@ -650,44 +528,79 @@ static MsdLayout msd_layout(ii_ctx* c) {
 }
 static constexpr size_t kMsdBytes = sizeof(uint64_t) * (3 * (size_t)kMsdMax + 2 + 4 * (size_t)kMsdMax * kRadix);
 
-// The token sort of local_reduce in the packed form: k_sort0_compact (dedup,
-// key remap, compaction, counts of the top digit per workgroup) into *k2, the
-// MSD scatter into buckets of u32 records (*k, padded), per-bucket digit
-// counts, two bucket-local onesweep passes (*k -> *k2 -> *k, both writing u32
-// records in the padded buckets; K3 reads that layout).  Keys sit at bits
-// [lo, lo + W) of the records, ids below 2^F.  On return *k holds the *n_out
-// sorted records.
-static int run_sort_packed(ii_ctx* c, uint64_t** k, uint64_t** k2, uint64_t n, int lo, int W, int F, int m,
-                           const uint32_t* remap0, uint64_t* n_out, bool wid, int* passes) {
-    *passes = 0;
-    *n_out = n;
+// Sorted (key, id) records as K3 reads them (run_unique): n u64 records key << 32 | id, or in the
+// packed layout u32 records key's low L bits << F | id in nb padded buckets (one per top digit; bucket
+// geometry in c->msd, every tile's bucket in c->tbk) of ntb tiles, ncap records, at most.
+struct SortedRecs {
+    const uint64_t* r = nullptr;
+    uint64_t n = 0;
+    bool packed = false;
+    uint32_t nb = 0, ntb = 0;
+    uint64_t ncap = 0;
+    int F = 0, L = 0;
+};
+constexpr int kRecKeyShift = 32;  // K1's records: the key's bit 0
+static_assert(kPlanRadixBits == kRadixBits && kPlanMsdMaxBits == kMsdMaxBits, "ii_sortplan.h restates the digit widths");
+
+// The token sort of local_reduce in the u64 form (plan m = 0): the first pass leaves each workgroup's
+// kept records in k2, its scatter reads the kept ranges back into k sorted by the first digit, and the
+// remaining LSD passes run over the kept records only (the exact wid range narrows them) — onesweep
+// passes when their digits fit the histograms k_sort0_compact keeps, histogram passes otherwise.
+static int token_sort_u64(ii_ctx* c, const TokenSortPlan& p, uint64_t* k, uint64_t* k2, uint64_t n, SortedRecs* out,
+                          uint64_t* c0_bytes, int* passes) {
+    const int lo = kRecKeyShift;
+    int hi = lo + p.W;
+    const int npass = (p.W + kRadixBits - 1) / kRadixBits, bits = (p.W + npass - 1) / npass;
+    const bool sweep = npass - 1 <= kLaterDigits;
+    uint64_t* dhist = nullptr;
+    if (sweep) {
+        CK(grow(c->dhist, sizeof(uint64_t) * 2 * kLaterDigits * kRadix));
+        dhist = P_<uint64_t>(c->dhist);
+        HIPCK(hipMemsetAsync(dhist, 0, sizeof(uint64_t) * kLaterDigits * kRadix, c->st));
+    }
+    uint64_t nch;
+    CK(sort0_pass(c, p, k, k2, lo, (1u << bits) - 1u, kRadix, lo + bits, lo + 2 * bits, dhist, &nch));
+    if (sweep) k_digit_bases<<<kLaterDigits, kRadix, 0, c->st>>>(dhist, dhist + kLaterDigits * kRadix);
+    const bool ev = c->n_sc < kMaxTimedPasses;
+    if (ev) HIPCK(hipEventRecord(c->ev_sc[2 * c->n_sc], c->st));
+    k_radix_scatter<false, kScatterThreads, kScatterItems><<<(uint32_t)nch, kScatterThreads, 0, c->st>>>(
+        k2, k, nullptr, nullptr, n, 0, lo, bits, (uint32_t)nch, P_<uint64_t>(c->rtable), P_<uint64_t>(c->kept), nullptr,
+        nullptr, 0, 0u);
+    if (ev) HIPCK(hipEventRecord(c->ev_sc[2 * c->n_sc + 1], c->st));
+    HIPCK(hipGetLastError());
+    *passes = 1;
+    uint64_t t47[5];
+    CK(read_u64(c, P_<uint64_t>(c->totals) + 4, t47, 5));
+    n = sort0_counts(c, p, t47, n, c0_bytes);
+    if (p.wid) hi = std::min(hi, lo + std::max(1, bitlen(c->NW - 1)));
+    if (ev) c->sc_bytes[c->n_sc++] = 16 * n;
+    if (n > 1 && !sweep) CK(hist_passes(c, &k, &k2, nullptr, nullptr, n, lo + bits, hi, bits, true, passes));
+    // (onesweep: one launch per pass, no histogram pass, no table scan)
+    for (int shift = lo + bits, pass = 1; n > 1 && sweep && shift < hi; shift += bits, pass++)
+        CK(sweep_pass(c, &k, &k2, nullptr, nullptr, n, shift, std::min(bits, hi - shift),
+                      dhist + (uint64_t)(kLaterDigits + pass - 1) * kRadix, true, passes));
+    *out = SortedRecs{k, n};
+    return II_OK;
+}
+
+// The token sort of local_reduce in the packed form (plan m > 0): the first pass (with counts of the
+// top digit per workgroup) into k2, the MSD scatter into buckets of u32 records (k, padded), per-bucket
+// digit counts, two bucket-local onesweep passes (k -> k2 -> k, both writing u32 records in the padded
+// buckets; K3 reads that layout).
+static int token_sort_packed(ii_ctx* c, const TokenSortPlan& p, uint64_t* k, uint64_t* k2, uint64_t n, SortedRecs* out,
+                             uint64_t* c0_bytes, int* passes) {
+    const int m = p.m, F = p.F;
     const uint32_t nb = 1u << m;
-    const int L = W - m, b0 = L - L / 2, b1 = L / 2;
-    const bool wide = m > kRadixBits;  // (k_sort0_compact<.., kWideD>, k_msd_scatter_wide)
-    const uint32_t rows = wide ? nb : kRadix;  // digit rows of the table
-    S0Geom s0{};
-    CK(s0_geometry(c, &s0));
-    const uint64_t nch = s0.ncol;
-    CK(grow(c->rtable, sizeof(uint64_t) * rows * kMaxChunks));
-    CK(grow(c->kept, sizeof(uint64_t) * 2 * kMaxChunks));
+    const int L = p.W - m, b0 = L - L / 2, b1 = L / 2;
     CK(grow(c->msd, kMsdBytes));
-    const MsdLayout g = msd_layout(c);
-    uint64_t* bstart = g.bstart;
-    uint64_t* pad = g.pad;
-    uint32_t* btile = g.btile;
-    uint64_t* gh = g.gh;
-    uint64_t* gbase = g.gbase;
-    uint64_t* table = P_<uint64_t>(c->rtable);
-    uint64_t* kept = P_<uint64_t>(c->kept);
+    const auto [bstart, pad, gh, gbase, btile] = msd_layout(c);
     uint64_t* totals = P_<uint64_t>(c->totals);
     unsigned long long* err = P_<unsigned long long>(c->counters) + C_OVERFLOW;
-    const int shift = lo + L;  // the top digit of the key
-    const uint32_t dmask = nb - 1u;
-
-    HIPCK(hipEventRecord(c->ev_c0[0], c->st));
-    launch_sort0(c, s0, wid, *k, *k2, shift, dmask, table, remap0, kept, 0, 0, nullptr, wide, dedup_by_set(c, n));
-    HIPCK(hipEventRecord(c->ev_c0[1], c->st));
-    CK(run_scan(c, OpInPlace{table}, (uint64_t)rows * nch, totals + 4));
+    const int shift = kRecKeyShift + L;  // the top digit of the key
+    uint64_t nch;
+    CK(sort0_pass(c, p, k, k2, shift, nb - 1u, p.wide ? nb : kRadix, 0, 0, nullptr, &nch));
+    uint64_t* table = P_<uint64_t>(c->rtable);
+    uint64_t* kept = P_<uint64_t>(c->kept);
     k_msd_geometry<<<1, kRadix, 0, c->st>>>(table, (uint32_t)nch, nb, totals + 4, kSweepTile, bstart, btile, pad);
     HIPCK(hipMemsetAsync(gh, 0, sizeof(uint64_t) * 2 * nb * kRadix, c->st));
     HIPCK(hipGetLastError());
@@ -695,66 +608,62 @@ static int run_sort_packed(ii_ctx* c, uint64_t** k, uint64_t** k2, uint64_t n, i
     // MSD scatter: u64 records -> u32 records in padded buckets
     const bool ev = c->n_sc + 3 <= kMaxTimedPasses;
     if (ev) HIPCK(hipEventRecord(c->ev_sc[2 * c->n_sc], c->st));
-    uint32_t* out32 = reinterpret_cast<uint32_t*>(*k);
+    uint32_t* out32 = reinterpret_cast<uint32_t*>(k);
     constexpr int NTs = kScatterThreads, ITs = kScatterItems;
     // (for 8-bit top digits k_msd_scatter<.., 256> measured 0.1 ms slower than k_radix_scatter<kPack>, also
     // with 8- or 12-record tiles at 6 waves per SIMD, 3 workgroups per CU)
-    if (wide) {
+    if (p.wide) {
         // 2048 digits: 256 threads x 32 records and u32 run bases when every position of the padded
         // layout fits (76 KiB of LDS, two workgroups per CU), else 512 x 32 with u64 bases (148 KiB)
         const bool run32 = n + (uint64_t)nb * kSweepTile < (1ull << 32);
         if (m > 10 && run32)
             k_msd_scatter<NTs / 2, 2 * ITs, kMsdMax, true><<<(uint32_t)nch, NTs / 2, 0, c->st>>>(
-                *k2, out32, shift, m, (uint32_t)nch, table, kept, pad, F, (1u << L) - 1u);
+                k2, out32, shift, m, (uint32_t)nch, table, kept, pad, F, (1u << L) - 1u);
         else
             (m <= 9 ? k_msd_scatter<NTs, ITs, 512> : m <= 10 ? k_msd_scatter<NTs, ITs, 1024>
                     : k_msd_scatter<NTs, 2 * ITs, kMsdMax>)<<<(uint32_t)nch, NTs, 0, c->st>>>(
-                *k2, out32, shift, m, (uint32_t)nch, table, kept, pad, F, (1u << L) - 1u);
+                k2, out32, shift, m, (uint32_t)nch, table, kept, pad, F, (1u << L) - 1u);
     } else {
         k_radix_scatter<false, kScatterThreads, kScatterItems, true><<<(uint32_t)nch, kScatterThreads, 0, c->st>>>(
-            *k2, (uint64_t*)nullptr, nullptr, nullptr, n, 0, shift, m, (uint32_t)nch, table, kept,
-            reinterpret_cast<uint32_t*>(*k), pad, F, (1u << L) - 1u);
+            k2, (uint64_t*)nullptr, nullptr, nullptr, n, 0, shift, m, (uint32_t)nch, table, kept, out32, pad, F,
+            (1u << L) - 1u);
     }
     if (ev) HIPCK(hipEventRecord(c->ev_sc[2 * c->n_sc + 1], c->st));
     HIPCK(hipGetLastError());
     uint64_t t47[5];
     CK(read_wait(c, t47, 4, 5));
-    const uint64_t n_in = n;
-    n = t47[0];
-    if (wid) c->NW = kHotSlots + (c->V - (t47[3] & 0xFFFFFFFFull));  // exact wid range (k_count_hot)
-    c->c0_bytes = s0_bytes(n_in, t47[4], n);
-    *n_out = n;
+    n = sort0_counts(c, p, t47, n, c0_bytes);
     if (ev) c->sc_bytes[c->n_sc++] = 12 * n;
     *passes = 1;
+    *out = SortedRecs{k, n};
     if (n == 0) return II_OK;
     // per-bucket digit counts of the two LSD passes -> bases
-    c->sort_packed = true;
-    c->sort_hist_bytes = 4 * n;
-    c->pk_nb = nb;
-    c->pk_F = F;
-    c->pk_L = L;
     const uint64_t ntb = (n + kSweepTile - 1) / kSweepTile + nb;  // tiles of the padded layout, at most
     const uint32_t hg = (uint32_t)std::min<uint64_t>(kMaxChunks, ntb);
     const uint32_t per = (uint32_t)((ntb + hg - 1) / hg);
-    c->pk_ntb = (uint32_t)ntb;
-    c->pk_ncap = ntb * kSweepTile;
+    out->packed = true;
+    out->nb = nb;
+    out->ntb = (uint32_t)ntb;
+    out->ncap = ntb * kSweepTile;  // u32 records K3 may load (the padded layout's extent)
+    out->F = F;
+    out->L = L;
     CK(grow(c->tbk, sizeof(uint16_t) * ntb));
     uint16_t* tbk = P_<uint16_t>(c->tbk);
     k_tile_buckets<<<nb, kBlock, 0, c->st>>>(btile, tbk);
     k_seg_hist<kSweepThreads, kSweepItems><<<hg, kSweepThreads, 0, c->st>>>(
-        reinterpret_cast<const uint32_t*>(*k), btile, bstart, nb, per, F, b0, F + b0, b1, gh);
+        reinterpret_cast<const uint32_t*>(k), btile, bstart, nb, per, F, b0, F + b0, b1, gh);
     k_digit_bases<<<2 * nb, kRadix, 0, c->st>>>(gh, gbase);
     HIPCK(hipGetLastError());
     // two bucket-local onesweep passes, both u32 -> u32 in the padded buckets (K3 reads that layout)
-    for (int p = 0; p < 2; p++) {
+    for (int pass = 0; pass < 2; pass++) {
         CK(lookback_pass(c, ntb * kRadix));
         const bool evp = c->n_sc < kMaxTimedPasses;
         if (evp) HIPCK(hipEventRecord(c->ev_sc[2 * c->n_sc], c->st));
         k_onesweep_seg<kSweepThreads, kSweepItems><<<(uint32_t)ntb, kSweepThreads, 0, c->st>>>(
-            reinterpret_cast<const uint32_t*>(p == 0 ? *k : *k2), ntb * kSweepTile,
-            reinterpret_cast<uint32_t*>(p == 0 ? *k2 : *k), btile,
-            tbk, bstart, nb, p == 0 ? F : F + b0, p == 0 ? b0 : b1, gbase + p * kRadix, 2 * kRadix, P_<uint64_t>(c->lbstat),
-            P_<uint32_t>(c->ticket), c->lb_epoch, err);
+            reinterpret_cast<const uint32_t*>(pass == 0 ? k : k2), ntb * kSweepTile,
+            reinterpret_cast<uint32_t*>(pass == 0 ? k2 : k), btile, tbk, bstart, nb, pass == 0 ? F : F + b0,
+            pass == 0 ? b0 : b1, gbase + pass * kRadix, 2 * kRadix, P_<uint64_t>(c->lbstat), P_<uint32_t>(c->ticket),
+            c->lb_epoch, err);
         if (evp) {
             HIPCK(hipEventRecord(c->ev_sc[2 * c->n_sc + 1], c->st));
             c->sc_bytes[c->n_sc++] = 8 * n;
@@ -765,12 +674,14 @@ static int run_sort_packed(ii_ctx* c, uint64_t** k, uint64_t** k2, uint64_t n, i
     return II_OK;
 }
 
-// K3: distinct (lexid, id0) pairs of the sorted records r[0, n), their
+// K3: distinct (lexid, id0) pairs of the sorted records s, their
 // posting byte offsets (P[U] = all posting bytes) and each word's first pair
 // (post_start[V] = U).  Sets c->U.  fmap: id0 of every shard-local file index
 // the records carry (null: the records carry id0 - fid_off).
-static int run_unique(ii_ctx* c, const uint64_t* r, uint64_t n, bool wid, bool packed, const uint32_t* fmap,
-                      bool compact, uint32_t fid_off = 0) {
+static int run_unique(ii_ctx* c, const SortedRecs& s, bool wid, const uint32_t* fmap, bool compact,
+                      uint32_t fid_off = 0) {
+    const uint64_t* r = s.r;
+    const uint64_t n = s.n;
     c->xpairs = false;
     if (compact && c->id_bound > kPairFirst) compact = false;  // (the top bit marks a word's first pair: u64 pairs)
     c->pairs32 = compact;
@@ -808,15 +719,15 @@ static int run_unique(ii_ctx* c, const uint64_t* r, uint64_t n, bool wid, bool p
         pe_k = P_<uint64_t>(c->pstop_w);
     }
     // one pass with decoupled look-back (k_uniq_sweep): U -> post_start[V], posting bytes -> totals[6]
-    if (packed) {  // r: the packed sort's u32 records in their padded buckets (k_uniq_sweep<true>)
+    if (s.packed) {  // r: the packed sort's u32 records in their padded buckets (k_uniq_sweep<true>)
         const MsdLayout g = msd_layout(c);
         const uint64_t* bstart = g.bstart;
         const uint32_t* btile = g.btile;
-        const uint64_t ntiles = 2ull * c->pk_ntb;  // at most: the spare ones leave at once
+        const uint64_t ntiles = 2ull * s.ntb;  // at most: the spare ones leave at once
         CK(lookback_pass(c, 2 * ntiles));
         (fmap ? k_uniq_sweep<true, true> : k_uniq_sweep<true, false>)<<<(uint32_t)ntiles, kBlock, 0, c->st>>>(
-            nullptr, n, reinterpret_cast<const uint32_t*>(r), c->pk_ncap, btile, P_<uint16_t>(c->tbk), bstart, c->pk_nb, c->pk_F, c->pk_L, uniq, Pp, ps_k,
-            pe_k, P_<uint64_t>(c->lbstat), P_<uint32_t>(c->ticket), c->lb_epoch, ps + c->V, totals + 6,
+            nullptr, n, reinterpret_cast<const uint32_t*>(r), s.ncap, btile, P_<uint16_t>(c->tbk), bstart, s.nb, s.F, s.L, uniq,
+            Pp, ps_k, pe_k, P_<uint64_t>(c->lbstat), P_<uint32_t>(c->ticket), c->lb_epoch, ps + c->V, totals + 6,
             P_<unsigned long long>(c->counters) + C_OVERFLOW, fmap, u32, g64, c->dth, fid_off);
     } else {
         const uint64_t ntiles = (n + kUniqSweepTile - 1) / kUniqSweepTile;
@@ -843,6 +754,52 @@ static int run_unique(ii_ctx* c, const uint64_t* r, uint64_t n, bool wid, bool p
     if (fu[0] & kLbTimeout) return II_ERR_INTERNAL;
     HIPCK(hipMemcpyAsync(Pp + c->U, totals + 6, sizeof(uint64_t), hipMemcpyDeviceToDevice, c->st));
     return II_OK;
+}
+
+// ----------------------------------------------------------------- knobs
+// Every environment switch of the library (test and A/B knobs; DESIGN §7 names each one's test), read by the call
+// named above its group: ii_open once per context, the others at the start of every call (tests flip them between calls).
+struct Knobs {
+    // ii_open
+    int test_lb_timeout = 0;    // II_TEST_LB_TIMEOUT=1|sort|sweep|order -> 1 .. 4 (ii_ctx::test_lb_timeout)
+    bool test_collide = false;  // II_TEST_COLLIDE=1: the context's first exactness check reports a collision
+    int test_long_bits = 64;    // II_TEST_LONG_KEY_BITS=b: the first map hashes long words to b bits
+    int table_log2 = 0;         // II_TABLE_LOG2=10..30: big-table slots, fixed (never shrunk); 0: sized by the input
+    // map_core
+    int rec_layout = 0;  // II_REC_LAYOUT=dense|fixed -> 1 | 2: K1's record layout; 0: fixed capacity if memory allows
+    // II_NARROW_KEYS=<n>: less room for fast-path miss keys in a narrow chunk (drives the overflow path on ordinary corpora)
+    uint32_t narrow_keys = (uint32_t)kNarrowKeys;
+    // local_reduce
+    bool lexid_keys = false;  // II_SORT_KEYS=lexid: the token sort by lexid also where word ids would do
+    // II_DICT_SIDE=0: the dictionary's lexicographic part in stream order, not beside the token sort
+    // (same-box A/B: 394.0-394.5 GB/s with the dictionary in stream order, 395.6-396.3 beside the sort)
+    bool dict_side = true;
+    SortKnobs sort;  // II_PACKED_SORT, II_PACKED_M, II_S0_DEDUP, II_S0_FMAP (ii_sortplan.h)
+    // local_reduce, ii_import
+    bool no_sweep = false;  // II_SORT_NO_SWEEP (set): the generic sorts as histogram passes, never onesweep passes
+    // ii_import
+    int import_id_sort = 0;  // II_IMPORT_ID_SORT (set) -> 1, =64 -> 64: radix-sort the received pairs (u64 form)
+    // ii_query
+    int query_tile_log2 = 0;  // II_QUERY_TILE=<power of two >= 64>: postings per work item (default kQueryTile)
+};
+static Knobs read_knobs() {
+    Knobs k;
+    const char* e = getenv("II_TEST_LB_TIMEOUT");
+    if (e) k.test_lb_timeout = !strcmp(e, "1") ? 1 : !strcmp(e, "sort") ? 2 : !strcmp(e, "sweep") ? 3 : !strcmp(e, "order") ? 4 : 0;
+    k.test_collide = (e = getenv("II_TEST_COLLIDE")) && !strcmp(e, "1");
+    if ((e = getenv("II_TEST_LONG_KEY_BITS"))) k.test_long_bits = std::min(64, std::max(0, atoi(e)));
+    if ((e = getenv("II_TABLE_LOG2")) && atoi(e) >= 10 && atoi(e) <= 30) k.table_log2 = atoi(e);
+    if ((e = getenv("II_REC_LAYOUT"))) k.rec_layout = !strcmp(e, "dense") ? 1 : !strcmp(e, "fixed") ? 2 : 0;
+    if ((e = getenv("II_NARROW_KEYS")) && *e) k.narrow_keys = (uint32_t)std::min<unsigned long>(strtoul(e, nullptr, 10), kNarrowKeys);
+    k.lexid_keys = (e = getenv("II_SORT_KEYS")) && !strcmp(e, "lexid");
+    k.dict_side = !((e = getenv("II_DICT_SIDE")) && !strcmp(e, "0"));
+    k.sort = parse_sort_knobs(getenv("II_PACKED_SORT"), getenv("II_PACKED_M"), getenv("II_S0_DEDUP"), getenv("II_S0_FMAP"));
+    k.no_sweep = getenv("II_SORT_NO_SWEEP") != nullptr;
+    if ((e = getenv("II_IMPORT_ID_SORT"))) k.import_id_sort = !strcmp(e, "64") ? 64 : 1;
+    k.query_tile_log2 = bitlen(kQueryTile) - 1;
+    const long v = (e = getenv("II_QUERY_TILE")) ? atol(e) : 0;
+    if (v >= 64 && v <= (1l << 30) && (v & (v - 1)) == 0) k.query_tile_log2 = bitlen((uint64_t)v) - 1;
+    return k;
 }
 
 // ----------------------------------------------------------------- lifecycle
@@ -877,16 +834,12 @@ extern "C" int ii_open(ii_ctx** out, int device) {
         ii_close(c);
         return II_ERR_NOMEM;
     }
-    if (const char* e = getenv("II_TEST_LB_TIMEOUT")) c->test_lb_timeout = !strcmp(e, "1")       ? 1
-                                                                : !strcmp(e, "sort")  ? 2
-                                                                : !strcmp(e, "sweep") ? 3
-                                                                : !strcmp(e, "order") ? 4
-                                                                                      : 0;
-    c->test_collide = getenv("II_TEST_COLLIDE") && !strcmp(getenv("II_TEST_COLLIDE"), "1");
-    if (getenv("II_TEST_LONG_KEY_BITS")) c->test_long_bits = std::min(64, std::max(0, atoi(getenv("II_TEST_LONG_KEY_BITS"))));
-    const char* s = getenv("II_TABLE_LOG2");
-    if (s && atoi(s) >= 10 && atoi(s) <= 30) {
-        c->big_cap = 1ull << atoi(s);
+    const Knobs kn = read_knobs();
+    c->test_lb_timeout = kn.test_lb_timeout;
+    c->test_collide = kn.test_collide;
+    c->test_long_bits = kn.test_long_bits;
+    if (kn.table_log2) {
+        c->big_cap = 1ull << kn.table_log2;
         c->big_fixed = true;
     }
     memset(&c->stats, 0, sizeof(c->stats));
@@ -963,11 +916,9 @@ extern "C" const char* ii_strerror(int code) {
 // K1 record layout: the fixed-capacity one (no counting pass) unless
 // II_REC_LAYOUT=dense or its buffers (12 B per K1b token slot, 6 B per text
 // byte) would take more than 40% of the device memory left.
-static bool use_fixed_capacity(ii_ctx* c, uint64_t nch, bool dense) {
-    if (dense) return false;
-    const char* e = getenv("II_REC_LAYOUT");
-    if (e && !strcmp(e, "dense")) return false;
-    if (e && !strcmp(e, "fixed")) return true;
+static bool use_fixed_capacity(ii_ctx* c, uint64_t nch, bool dense, const Knobs& kn) {
+    if (dense || kn.rec_layout == 1) return false;
+    if (kn.rec_layout == 2) return true;
     size_t fr = 0, tot = 0;
     if (!hip_ok(hipMemGetInfo(&fr, &tot))) {
         (void)hipGetLastError();
@@ -977,15 +928,6 @@ static bool use_fixed_capacity(ii_ctx* c, uint64_t nch, bool dense) {
     return 12.0 * (double)nch * (double)kChunkCap <= 0.4 * ((double)fr + held);
 }
 
-// Room for fast-path miss keys in a narrow chunk (kNarrowKeys); tests lower it
-// with II_NARROW_KEYS to drive the overflow path on ordinary corpora.
-static uint32_t narrow_keys() {
-    const char* e = getenv("II_NARROW_KEYS");
-    if (!e || !*e) return (uint32_t)kNarrowKeys;
-    const unsigned long v = strtoul(e, nullptr, 10);
-    return v < kNarrowKeys ? (uint32_t)v : (uint32_t)kNarrowKeys;
-}
-
 // dense: records of token k at rec[k] (the import path indexes them so).
 // The main map (not dense) leaves the exactness check of its hashed keys
 // (k_long_verify) running on the side stream while the reduce proceeds on the
@@ -993,6 +935,7 @@ static uint32_t narrow_keys() {
 // re-runs map + reduce with a new seed on a collision.  The import's word
 // map checks at once.
 static int map_core(ii_ctx* c, uint64_t hist_out[II_ALPHABET], bool dense = false) {
+    const Knobs kn = read_knobs();
     // a check of an earlier map still reads the table, the long queue and the counters
     if (c->lv_pending) HIPCK(hipStreamWaitEvent(c->st, c->ev_res[1], 0));
     c->lv_pending = false;
@@ -1001,14 +944,14 @@ static int map_core(ii_ctx* c, uint64_t hist_out[II_ALPHABET], bool dense = fals
     c->planned_parts = 0;
     c->host_valid = false;
     c->n_sc = 0;
-    c->c0_bytes = 0;
+    c->last_sort.c0_bytes = 0;
     c->retries = 0;
     memset(&c->stats, 0, sizeof(c->stats));
     uint64_t* counters = P_<uint64_t>(c->counters);
     uint64_t* totals = P_<uint64_t>(c->totals);
     HIPCK(hipEventRecord(c->ev[0], c->st));
     HIPCK(hipMemsetAsync(counters, 0, sizeof(uint64_t) * C_NUM, c->st));
-    c->T = c->V = c->U = c->nlong = c->T_sorted = 0;
+    c->T = c->V = c->U = c->nlong = c->last_sort.T_sorted = 0;
     if (c->nbytes == 0 || c->nfiles == 0) {
         memset(c->hist, 0, sizeof(c->hist));
         if (hist_out) memset(hist_out, 0, sizeof(uint64_t) * II_ALPHABET);
@@ -1044,7 +987,7 @@ static int map_core(ii_ctx* c, uint64_t hist_out[II_ALPHABET], bool dense = fals
     HIPCK(hipMemsetAsync(totals + 8, 0, 2 * sizeof(uint64_t), c->st));
     k_check_layout<<<grid_for(c->nfiles), kBlock, 0, c->st>>>(c->text, fstart, c->nfiles, totals + 9);
     HIPCK(hipMemsetAsync(chunk_cnt + nch, 0, sizeof(uint64_t), c->st));  // voff[nch] = T after the scan
-    c->rec_cap = use_fixed_capacity(c, nch, dense) ? kChunkCap : 0;
+    c->rec_cap = use_fixed_capacity(c, nch, dense, kn) ? kChunkCap : 0;
     if (c->rec_cap) {
         CK(grow(c->rec, std::max(sizeof(uint64_t) * nch * kChunkCap, packed_bytes(nch * kChunkCap))));
         CK(grow(c->pend, sizeof(uint32_t) * nch * kChunkCap));
@@ -1088,7 +1031,7 @@ static int map_core(ii_ctx* c, uint64_t hist_out[II_ALPHABET], bool dense = fals
         const uint64_t long_mask = c->test_long_bits < 64 && c->collide_retries == 0 ? (1ull << c->test_long_bits) - 1ull : ~0ull;
         Table tab{P_<unsigned long long>(c->tkeys), P_<uint64_t>(c->trep), c->big_cap - 1, c->seed, counters, long_mask};
         HIPCK(hipEventRecord(c->ev_emit[0], c->st));
-        const uint32_t nkeys = narrow_keys();
+        const uint32_t nkeys = kn.narrow_keys;
         c->map_deep = c->deep_probe;
         auto* emit = nkeys == kNarrowKeys ? (c->deep_probe ? k_tok_emit<false, true> : k_tok_emit<false, false>)
                                           : (c->deep_probe ? k_tok_emit<true, true> : k_tok_emit<true, false>);
@@ -1472,15 +1415,15 @@ static int dict_slots(ii_ctx* c, bool wid) {
         k_count_hot<<<grid_for(V), kBlock, 0, c->st>>>(dslot, V, nhot);
         k_wid_map<<<grid_for(V), kBlock, 0, c->st>>>(dslot, V, nhot, P_<uint32_t>(c->wmap));
         HIPCK(hipGetLastError());
-        c->NW = kHotSlots + V;  // bound; run_sort refines it from totals[7] after its first pass (no extra sync)
+        c->NW = kHotSlots + V;  // bound; the token sort refines it from totals[7] after its first pass (sort0_counts)
     }
     return II_OK;
 }
 
 // Dictionary, part 2: the lexicographic order of the V words (prefix-key
 // sort, ties of longer words), remap / lkey / lrep / llen / lstart, and for
-// word-id keys wid <-> lexid (lexw, widl).  Needs dict_slots' results.
-static int dict_lex(ii_ctx* c, bool wid) {
+// word-id keys wid <-> lexid (lexw, widl).  Needs dict_slots' results.  no_sweep: Knobs::no_sweep.
+static int dict_lex(ii_ctx* c, bool wid, bool no_sweep) {
     uint64_t* counters = P_<uint64_t>(c->counters);
     uint64_t* totals = P_<uint64_t>(c->totals);
     const uint32_t V = (uint32_t)c->V;
@@ -1492,7 +1435,10 @@ static int dict_lex(ii_ctx* c, bool wid) {
     uint32_t* di = P_<uint32_t>(c->didx);
     uint32_t* di2 = P_<uint32_t>(c->didx2);
     k_dict_keys<<<grid_for(V), kBlock, 0, c->st>>>(c->text, c->nbytes, keys, rep, dslot, V, sk, di);
-    CK(run_sort(c, &sk, &sk2, &di, &di2, V, 0, 64, false, nullptr));
+    SortOpts key_sort;  // (its look-back flag is read below, before di is used)
+    key_sort.sweep = !no_sweep;
+    const SortOpts tie_sort{};  // (histogram passes: no host read between them and k_tie_place's use of tv)
+    CK(run_sort(c, &sk, &sk2, &di, &di2, V, 0, 64, key_sort));
 
     // words sharing a 12-letter prefix (both longer than 12): order them by
     // their remaining letters (LSD over 12-letter chunks on the tied subset)
@@ -1531,12 +1477,11 @@ static int dict_lex(ii_ctx* c, bool wid) {
         for (uint32_t ch = kmax; ch >= 1; ch--) {
             k_tie_keys<<<grid_for(nt), kBlock, 0, c->st>>>(c->text, c->nbytes, tv, (uint32_t)nt, tdict, dslot, rep, rid,
                                                           rfirst, ch, tk);
-            CK(run_sort(c, &tk, &tk2, &tv, &tv2, nt, 0, 64, false, nullptr, nullptr, nullptr, false, false));
+            CK(run_sort(c, &tk, &tk2, &tv, &tv2, nt, 0, 64, tie_sort));
         }
         k_tie_keys<<<grid_for(nt), kBlock, 0, c->st>>>(c->text, c->nbytes, tv, (uint32_t)nt, tdict, dslot, rep, rid, rfirst,
                                                       0, tk);
-        CK(run_sort(c, &tk, &tk2, &tv, &tv2, nt, 0, std::max(1, bitlen(nt)), false, nullptr, nullptr, nullptr, false,
-                    false));
+        CK(run_sort(c, &tk, &tk2, &tv, &tv2, nt, 0, std::max(1, bitlen(nt)), tie_sort));
         k_tie_place<<<grid_for(nt), kBlock, 0, c->st>>>(tk, tv, (uint32_t)nt, tpos, tdict, di);
         HIPCK(hipGetLastError());
     }
@@ -1555,12 +1500,12 @@ static int dict_lex(ii_ctx* c, bool wid) {
 }
 
 // The whole dictionary in stream order (the owner's import; lexid-keyed sorts).
-static int build_dictionary(ii_ctx* c, bool wid = false) {
+static int build_dictionary(ii_ctx* c, bool wid, bool no_sweep) {
     CK(dict_slots(c, wid));
     uint64_t vchk;
     CK(read_u64(c, P_<uint64_t>(c->totals) + 1, &vchk));
     if (vchk != c->V) return II_ERR_INTERNAL;
-    return dict_lex(c, wid);
+    return dict_lex(c, wid, no_sweep);
 }
 
 // Local reduce: dictionary (lexicographic ids), K2 token sort, K3 unique
@@ -1569,8 +1514,7 @@ static int build_dictionary(ii_ctx* c, bool wid = false) {
 // wid: sort by word id (single-GPU reduce, k_wid_finish) instead of lexid;
 // the exchange path needs letter-contiguous pairs and sorts by lexid.
 static int local_reduce(ii_ctx* c, bool wid, bool compact) {
-    uint64_t* totals = P_<uint64_t>(c->totals);
-    (void)totals;
+    const Knobs kn = read_knobs();
     c->n_sc = 0;
     const uint64_t T = c->T, V = c->V;
     int sort_passes = 0;
@@ -1581,57 +1525,30 @@ static int local_reduce(ii_ctx* c, bool wid, bool compact) {
         return II_OK;
     }
     // ---- dictionary: lexicographic ids
-    if (getenv("II_SORT_KEYS") && !strcmp(getenv("II_SORT_KEYS"), "lexid")) wid = false;
+    if (kn.lexid_keys) wid = false;
     // word-id keys: the token sort needs only the slot part of the dictionary;
     // its lexicographic part (a sort of the V prefix keys, ~0.5 ms of small
     // launches and host round trips) runs on st2 beside the sort, queued once
     // the sort is; K3's word-id -> lexid step waits for it
-    const bool dict_side = wid && !(getenv("II_DICT_SIDE") && !strcmp(getenv("II_DICT_SIDE"), "0"));  // (same-box A/B: 394.0-394.5 GB/s with the dictionary in stream order, 395.6-396.3 beside the sort)
+    const bool dict_side = wid && kn.dict_side;
     if (dict_side) {
         CK(dict_slots(c, true));
         HIPCK(hipEventRecord(c->ev_dict[0], c->st));
-    } else if (wid) {
-        CK(build_dictionary(c, true));
     } else {
-        CK(build_dictionary(c, false));
+        CK(build_dictionary(c, wid, kn.no_sweep));
     }
     HIPCK(hipEventRecord(c->ev[2], c->st));
 
-    // ---- K2: sort records by (lexid, fid); fid order is kept by stability
-    uint64_t* r = P_<uint64_t>(c->rec);
-    uint64_t* r2 = P_<uint64_t>(c->rec2);
-    const int lb = std::max(1, bitlen((wid ? c->NW : V) - 1));
-    uint64_t Tk = T;
-    // the records carry shard-local file indices (k_chunk_files): F bits for this map's files
-    int F = std::max(1, bitlen(c->nfiles ? c->nfiles - 1 : 0));
-    // many small files with non-consecutive ids (a size-sorted ii_partition share): the first pass
-    // (its record-set form) writes id0s (F = their bits) when the packed form still holds them —
-    // K3's gather of fmap[index], in word order, missed L1 on nearly every pair (II_S0_FMAP=0|1:
-    // A/B and test knob)
-    bool s0map = false;
-    if (!c->fid_affine && c->id_bound && dedup_by_set(c, T)) {
-        const int Fg = std::max(1, bitlen(c->id_bound - 1));
-        const char* e = getenv("II_S0_FMAP");
-        if ((e ? strcmp(e, "0") != 0 : c->nfiles >= kS0FmapFiles) && packed_top_bits(lb, Fg)) {
-            F = Fg;
-            s0map = true;
-        }
-    }
-    c->sort_packed = false;
-    c->sort_W = lb;
-    c->sort_F = F;
-    const int m = packed_top_bits(lb, F);
-    if (m) {
-        c->s0_fmap = s0map ? P_<uint32_t>(c->fid) : nullptr;
-        const int rc = run_sort_packed(c, &r, &r2, T, 32, lb, F, m, P_<uint32_t>(wid ? c->wmap : c->remap), &Tk, wid,
-                                       &sort_passes);
-        c->s0_fmap = nullptr;
-        CK(rc);
-    } else
-        CK(run_sort(c, &r, &r2, nullptr, nullptr, T, 32, 32 + lb, true, &sort_passes,
-                    P_<uint32_t>(wid ? c->wmap : c->remap), &Tk, wid));
-    c->rec_sorted = r;
-    c->T_sorted = Tk;
+    // ---- K2: sort records by (key, file); file order is kept by stability.  The records carry
+    // shard-local file indices (k_chunk_files); the plan says where they become id0s
+    TokenSortPlan plan;
+    if (plan_token_sort({T, c->nfiles, c->id_bound, c->fid_affine, std::max(1, bitlen((wid ? c->NW : V) - 1)), wid, kn.sort},
+                        &plan))
+        return II_ERR_INTERNAL;
+    SortedRecs recs;
+    uint64_t c0_bytes = 0;
+    CK((plan.m ? token_sort_packed : token_sort_u64)(c, plan, P_<uint64_t>(c->rec), P_<uint64_t>(c->rec2), T, &recs,
+                                                     &c0_bytes, &sort_passes));
     // the next map's probe depth: DeepProbe when most distinct words live in the big table (NW = the
     // hot slots + the big-table words; wid keys only: lexid keys leave the choice as it was)
     if (wid) c->deep_probe = 2 * (c->NW - kHotSlots) > V;
@@ -1651,7 +1568,7 @@ static int local_reduce(ii_ctx* c, bool wid, bool compact) {
         {
             SideScope side(c);  // c->st is st2 in here
             HIPCK(hipStreamWaitEvent(c->st, c->ev_dict[0], 0));
-            CK(dict_lex(c, true));
+            CK(dict_lex(c, true, kn.no_sweep));
             HIPCK(hipEventRecord(c->ev_dict[1], c->st));
         }
         HIPCK(hipStreamWaitEvent(c->st, c->ev_dict[1], 0));
@@ -1669,8 +1586,8 @@ static int local_reduce(ii_ctx* c, bool wid, bool compact) {
         HIPCK(hipMemcpyAsync(c->hbuf, P_<uint64_t>(c->counters) + C_COLLIDE, sizeof(uint64_t), hipMemcpyDeviceToHost,
                              c->st));
     }
-    CK(run_unique(c, r, Tk, wid, c->sort_packed, c->fid_affine || s0map ? nullptr : P_<uint32_t>(c->fid), compact,
-                  c->fid_affine ? c->fid_off : 0u));
+    CK(run_unique(c, recs, wid, plan.ids == IdSource::GatherInK3 ? P_<uint32_t>(c->fid) : nullptr, compact,
+                  plan.ids == IdSource::Affine ? c->fid_off : 0u));
     if (check) {
         c->lv_pending = false;
         if (c->hbuf[0]) {  // (Las Vegas: the output never depends on the seed)
@@ -1685,6 +1602,7 @@ static int local_reduce(ii_ctx* c, bool wid, bool compact) {
     c->wid_pairs = wid;
     HIPCK(hipEventRecord(c->ev[4], c->st));
     c->stats.sort_passes = (uint32_t)sort_passes;
+    c->last_sort = SortStats{recs.packed, plan.W, plan.F, recs.packed ? 4 * recs.n : 0, c0_bytes, recs.n};
     c->have_pairs = true;
     return II_OK;
 }
@@ -1722,7 +1640,7 @@ static int order_and_format(ii_ctx* c, int copy_text) {
     k_order_keys<<<grid_for(V), kBlock, 0, c->st>>>(P_<uint64_t>(c->dkey), ps, pe, (uint32_t)V, dbits, ok, ov,
                                                     P_<uint32_t>(c->llen), Pp, loff);
     // (histogram passes: ov indexes loff / the formatter's tables before the host reads any flag)
-    CK(run_sort(c, &ok, &ok2, &ov, &ov2, V, 0, dbits + 5, false, nullptr, nullptr, nullptr, false, false));
+    CK(run_sort(c, &ok, &ok2, &ov, &ov2, V, 0, dbits + 5, SortOpts{}));
     if (c->test_lb_timeout == 4) k_set_bits<<<1, 1, 0, c->st>>>(P_<uint64_t>(c->counters) + C_OVERFLOW, kLbTimeout);
     c->ord = ov;
     HIPCK(hipEventRecord(c->ev[5], c->st));
@@ -1983,6 +1901,7 @@ extern "C" int ii_import(ii_ctx* c, int nparts, const void* d_recv, const uint64
     LIVE_OR_FAIL();
     HIPCK(hipSetDevice(c->dev));
     CK(settle_side(c));
+    const Knobs kn = read_knobs();
     std::vector<uint64_t> hdr(8 * (size_t)nparts);
     for (int s = 0; s < nparts; s++) {
         if (recv_off[s] & 7) return II_ERR_ARG;
@@ -2023,7 +1942,7 @@ extern "C" int ii_import(ii_ctx* c, int nparts, const void* d_recv, const uint64
         c->have_pairs = true;
         return II_OK;
     }
-    CK(build_dictionary(c));
+    CK(build_dictionary(c, false, kn.no_sweep));
     HIPCK(hipEventRecord(c->ev[2], c->st));
     uint64_t* wrec = P_<uint64_t>(c->rec);
     uint64_t* r = P_<uint64_t>(c->rec2);
@@ -2041,11 +1960,10 @@ extern "C" int ii_import(ii_ctx* c, int nparts, const void* d_recv, const uint64
         if (lo1 == 0 || hi1 < lo1 || lo1 <= prev_hi1) ordered = false;
         prev_hi1 = hi1;
     }
-    const char* ids_env = getenv("II_IMPORT_ID_SORT");
-    const bool id_sort = ids_env != nullptr;
+    const bool id_sort = kn.import_id_sort != 0;
     const bool scatter_runs = !id_sort && ordered;
     const int Fid = std::max(1, bitlen(id_bound ? id_bound - 1 : 0)), Lw = std::max(1, bitlen(c->V - 1));
-    const bool use32 = !scatter_runs && Lw + Fid <= 32 && !(id_sort && !strcmp(ids_env, "64"));
+    const bool use32 = !scatter_runs && Lw + Fid <= 32 && kn.import_id_sort != 64;
     // The pairs go to r (rec2) in every form: r2 is rec, which holds the word
     // records wrec every source's pairs are mapped through (writing records
     // there would overwrite word records later sources still read).
@@ -2109,14 +2027,21 @@ extern "C" int ii_import(ii_ctx* c, int nparts, const void* d_recv, const uint64
     } else if (id_sort && use32) {  // (test knob) r holds the u32 records (its second half is the ping-pong buffer)
         uint32_t* a = reinterpret_cast<uint32_t*>(r);
         uint32_t* b = a + ((NP + 3) & ~3ull);  // 16-B aligned: k_radix_hist reads 16 B at a time
-        CK(run_sort32(c, &a, &b, NP, Lw + Fid, &p1));
+        SortOpts o32;
+        o32.passes = &p1;
+        CK(run_sort(c, &a, &b, nullptr, nullptr, NP, 0, Lw + Fid, o32));
         // the word records are no longer read: the u64 records go to r2 (rec)
         k_unpack32<<<(uint32_t)std::min<uint64_t>(16384, grid_for(NP)), kBlock, 0, c->st>>>(a, NP, Fid, r2);
         HIPCK(hipGetLastError());
         std::swap(r, r2);
     } else if (id_sort) {  // (test knob) LSD over the id bits, then the word bits of the u64 records
-        CK(run_sort(c, &r, &r2, nullptr, nullptr, NP, 0, Fid, false, &p1));
-        CK(run_sort(c, &r, &r2, nullptr, nullptr, NP, 32, 32 + Lw, true, &p2));
+        SortOpts ids, words;
+        ids.sweep = !kn.no_sweep;
+        ids.passes = &p1;
+        words.timed = true;
+        words.passes = &p2;
+        CK(run_sort(c, &r, &r2, nullptr, nullptr, NP, 0, Fid, ids));
+        CK(run_sort(c, &r, &r2, nullptr, nullptr, NP, kRecKeyShift, kRecKeyShift + Lw, words));
     } else if (use32) {  // merge-path rounds over u32 records; K3 reads them as one bucket of the packed form
         uint32_t* a = reinterpret_cast<uint32_t*>(r);
         uint32_t* b = reinterpret_cast<uint32_t*>(r2);  // (rec: the word records are dead once mapped)
@@ -2128,14 +2053,10 @@ extern "C" int ii_import(ii_ctx* c, int nparts, const void* d_recv, const uint64
         HIPCK(hipMemsetAsync(c->tbk.p, 0, sizeof(uint16_t) * ntb, c->st));
         k_one_bucket<<<1, 1, 0, c->st>>>(g.bstart, g.btile, NP, (uint32_t)ntb);
         HIPCK(hipGetLastError());
-        c->pk_nb = 1;
-        c->pk_ntb = (uint32_t)ntb;
-        c->pk_ncap = NP;
-        c->pk_F = Fid;
-        c->pk_L = Lw;
+        const SortedRecs one{reinterpret_cast<const uint64_t*>(a), NP, true, 1, (uint32_t)ntb, NP, Fid, Lw};  // one bucket, unpadded
         HIPCK(hipEventRecord(c->ev[3], c->st));
         c->T = NP;
-        CK(run_unique(c, reinterpret_cast<const uint64_t*>(a), NP, false, true, nullptr, true));
+        CK(run_unique(c, one, false, nullptr, true));
         HIPCK(hipEventRecord(c->ev[4], c->st));
         c->stats.sort_passes = (uint32_t)p1;
         c->have_pairs = true;
@@ -2145,7 +2066,7 @@ extern "C" int ii_import(ii_ctx* c, int nparts, const void* d_recv, const uint64
     }
     HIPCK(hipEventRecord(c->ev[3], c->st));
     c->T = NP;
-    CK(run_unique(c, r, NP, false, false, nullptr, true));  // the owner's merged pairs: dense u64 records of id0s
+    CK(run_unique(c, SortedRecs{r, NP}, false, nullptr, true));  // the owner's merged pairs: dense u64 records of id0s
     HIPCK(hipEventRecord(c->ev[4], c->st));
     c->stats.sort_passes = (uint32_t)(p1 + p2);
     c->have_pairs = true;
@@ -2276,15 +2197,16 @@ extern "C" int ii_get_stats(ii_ctx* c, ii_stats* o) {
         s.scatter_launches = (uint32_t)c->n_sc;
         s.scatter_ms_avg = c->n_sc ? sum / c->n_sc : 0;
         s.scatter_bytes = c->n_sc ? bytes / c->n_sc : 0;  // per launch: bytes read + written
-        s.sort_bytes = bytes + (c->sort_packed ? c->sort_hist_bytes : 0);
-        s.sort_packed = c->sort_packed ? 1u : 0u;
+        const SortStats& ls = c->last_sort;
+        s.sort_bytes = bytes + (ls.sort_packed ? ls.sort_hist_bytes : 0);
+        s.sort_packed = ls.sort_packed ? 1u : 0u;
         s.pair_bytes = c->pairs32 ? 4u : 8u;
-        s.sort_key_bits = (uint32_t)c->sort_W;
-        s.sort_id_bits = (uint32_t)c->sort_F;
-        s.sorted_records = c->T_sorted;
-        if (c->c0_bytes) {
+        s.sort_key_bits = (uint32_t)ls.sort_W;
+        s.sort_id_bits = (uint32_t)ls.sort_F;
+        s.sorted_records = ls.T_sorted;
+        if (ls.c0_bytes) {
             s.sort0_ms = ev_ms(c->ev_c0[0], c->ev_c0[1]);
-            s.sort0_bytes = c->c0_bytes;
+            s.sort0_bytes = ls.c0_bytes;
         }
     }
     s.io_ms = c->io_ms;
@@ -2374,16 +2296,6 @@ extern "C" int ii_lookup(ii_ctx* c, const char* terms, const uint32_t* term_off,
     return II_OK;
 }
 
-// II_QUERY_TILE=<power of two >= 64> (test knob, read per call): postings per work item
-static int query_tile_log2() {
-    int lg = bitlen(kQueryTile) - 1;
-    if (const char* e = getenv("II_QUERY_TILE")) {
-        const long v = atol(e);
-        if (v >= 64 && v <= (1l << 30) && (v & (v - 1)) == 0) lg = bitlen((uint64_t)v) - 1;
-    }
-    return lg;
-}
-
 extern "C" int ii_query(ii_ctx* c, const char* terms, const uint32_t* term_off, const uint32_t* query_first,
                         uint32_t nqueries, int op, const uint64_t** res_off, const uint32_t** res_ids) {
     if (!c) return II_ERR_ARG;
@@ -2400,6 +2312,7 @@ extern "C" int ii_query(ii_ctx* c, const char* terms, const uint32_t* term_off, 
     LIVE_OR_FAIL();
     HIPCK(hipSetDevice(c->dev));
     const double t0 = now_ms();
+    const Knobs kn = read_knobs();
     const bool to_host = res_off != nullptr;
     c->q_valid = false;
     ii_query_stats qs;
@@ -2416,7 +2329,7 @@ extern "C" int ii_query(ii_ctx* c, const char* terms, const uint32_t* term_off, 
         if (to_host) c->h_q_roff.assign((size_t)nqueries + 1, 0);
     } else {
         CK(lookup_terms(c, terms, term_off, nterms));
-        const int tlg = query_tile_log2();
+        const int tlg = kn.query_tile_log2;
         CK(grow(c->q_first, sizeof(uint32_t) * ((size_t)nqueries + 1)));
         CK(grow(c->q_use, sizeof(uint32_t) * nterms));
         CK(grow(c->q_drv, sizeof(uint32_t) * nqueries));

@@ -628,6 +628,55 @@ def test_first_pass_file_id_map_vs_oracle(fm):
         os.environ.pop("II_S0_FMAP", None)
 
 
+def test_one_context_through_every_sort_form():
+    """One context through every form of the token sort in turn, then an
+    import, then the first form again: what a form leaves in the context (the
+    packed layout, the id map, the sort statistics) must not reach the next.
+    600 files of about 5·10^5 tokens (the record set by itself), ids sampled
+    from [0, 10^6) (not affine, 20 bits) or 0..599."""
+    import torch
+    t, off = ii_ctypes.zipf_corpus(3_000_000, 600, 50_000, 83, threads=8)
+    off = off.tolist()
+    sparse = sorted(random.Random(83).sample(range(1_000_000), 600))
+    dense = list(range(600))
+    exp = {id(sparse): oracle_index(t, off, sparse), id(dense): oracle_index(t, off, dense)}
+    knobs = ("II_S0_FMAP", "II_S0_DEDUP", "II_PACKED_SORT", "II_PACKED_M", "II_SORT_KEYS")
+    # (step, knobs, ids, sort_packed and sort_id_bits the statistics must show)
+    steps = [("a", {"II_S0_FMAP": "1"}, sparse, (1, 20)),
+             ("b", {"II_S0_FMAP": "0", "II_S0_DEDUP": "bitmap"}, sparse, (1, 10)),
+             ("c", {"II_PACKED_SORT": "0"}, sparse, (0, None)),
+             ("d", {"II_S0_FMAP": "1", "II_PACKED_M": "11"}, sparse, (1, 20)),
+             ("e", {}, dense, (1, 10)),
+             ("f", {"II_SORT_KEYS": "lexid"}, sparse, None),
+             ("g", None, sparse, None),
+             ("h", {"II_S0_FMAP": "1"}, sparse, (1, 20))]
+    try:
+        with ii_ctypes.Index(0) as ix, ii_ctypes.Index(0) as src:
+            for step, env, ids, want in steps:
+                for k in knobs:
+                    os.environ.pop(k, None)
+                if env is None:  # the single export part of a second context that holds the same corpus
+                    src.map_host(t, off, ids)
+                    src.reduce_local()
+                    size = src.export_plan(1)[0]
+                    buf = torch.empty(max(size, 8), dtype=torch.uint8, device="cuda")
+                    src.export(1, buf.data_ptr(), [0])
+                    ix.import_(1, buf.data_ptr(), [0], ids[-1] + 1)
+                else:
+                    os.environ.update(env)
+                    ix.map_host(t, off, ids)
+                ix.reduce()
+                assert_same(ix.letters(), exp[id(ids)], "step " + step)
+                if want:
+                    st = ix.stats()
+                    assert st.sort_packed == want[0], (step, st.sort_packed)
+                    if want[1] is not None:
+                        assert st.sort_id_bits == want[1], (step, st.sort_id_bits)
+    finally:
+        for k in knobs:
+            os.environ.pop(k, None)
+
+
 def test_dictionary_in_stream_order_vs_oracle():
     """II_DICT_SIDE=0: the dictionary's lexicographic part in stream order
     instead of beside the token sort (its side-stream placement is what every
